@@ -17,7 +17,13 @@ The top-level "roofline" is that of `value`'s own kernel, the fused NS model ste
 rocprofv3 counted for the same kernels ("traffic", "frac_hbm", from profiles/pmc_ns_fp32.json
 when it matches the kernel code and config).
 
-At N = 1 the line also carries, on the same graph generator:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does what `value` needs and no
+more: it builds the trainer, warms up, times the K steps and prints the result line. `--full` adds
+every other figure: the per-kernel times and rooflines of the NS step (eager profiled steps of
+their own) and, at N = 1, the full-graph leg and the CPU baselines below. `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+
+With `--full`, at N = 1 the line also carries, on the same graph generator:
   * "full_batch": the full-graph REGCN training step on mag_like(10) (input Linear, 2 x
     REGraphConv fwd+bwd, out_lin, CE, Adam) -- the REGraphConv SpMM whose HBM roofline
     north_star gates (>= 40 %), with its own "roofline": "frac" from the rocprofv3-counted HBM
@@ -30,6 +36,7 @@ At N = 1 the line also carries, on the same graph generator:
 Launch: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N, or
     python bench.py --gpus N (starts that launcher itself as a child process), or
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|mag|dblp|acm|imdb|...]
+                    [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -57,6 +64,31 @@ METRIC = "aggregated edges/sec per GPU (REGCN fwd+bwd, hidden=64); % HBM rooflin
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(args, outs):
+    """--dump-outputs DIR: rank 0 writes outs (name -> tensor: what the timed path computed in its
+    last step) as DIR/<name>.npy, float64 for float64 tensors and float32 for every other type,
+    flattened. All files together stay within DUMP_MAX_BYTES: an array over its equal share of
+    that is written as a fixed sample (elements at sorted indices from a generator seeded with
+    0), the same elements in every run with the same arguments."""
+    d = getattr(args, "dump_outputs", None)
+    if not d or _world()[0] != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(outs))
+    for name, t in outs.items():
+        t = t.detach().reshape(-1)
+        to = torch.float64 if t.dtype == torch.float64 else torch.float32
+        keep = share // (8 if to == torch.float64 else 4)
+        if t.numel() > keep:
+            idx = torch.randint(0, t.numel(), (keep,), generator=torch.Generator().manual_seed(0))
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.to(to).cpu().numpy())
+    log(f"[bench] wrote {', '.join(n + '.npy' for n in outs)} to {d}")
 
 
 def setup_dist(n):
@@ -168,6 +200,7 @@ def run_ns_epoch(args, dev):
     tr.run_steps(steps)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
+    dump_outputs(args, {"loss": tr.loss, "params": tr.param_vector()})
     model = info["model"].eval()
     si = ShardedInference(model, info["rg"], info["edge_type"], info["node_type"],
                           info["local"], rank, world)
@@ -279,22 +312,26 @@ def run_ns(args, dev):
     guard = Guard(world)
     tr, info = guard.stage("build the NS trainer (graph, features, model, sampler)",
                            lambda: build_ns(args, dev))
-    # per-op device times from eager profiled steps (events cannot sit inside a graph)
     for _ in range(max(1, args.warmup)):
         tr.guarded_step(guard)
-    profile.enable(True)
-    nsm_bytes = []
+    nsm_bytes, kstats = [], {}
+    # --full: per-op device times from eager profiled steps (events cannot sit inside a graph).
+    # A plain run takes the same five eager steps unprofiled (a few ms, no host sync): the timed
+    # steps then train the same batches from the same model with and without --full, so
+    # final_loss and --dump-outputs are comparable across the two kinds of run
+    profile.enable(args.full)
     for _ in range(5):
         tr.guarded_step(guard)
-        if tr.fused is not None:
+        if args.full and tr.fused is not None:
             nsm_bytes.append(ns_step_bytes(
                 tr.sampler.sizes.cpu().tolist(), 128, 349, rel_slots=bool(tr.fused.P.rel_slots),
                 two_layer=tr.fused.two_layer,
                 adam_params=tr.flat.numel() if tr.adam_fused else 0,
                 pre_sums=bool(tr.fused.W.pre_sums)))
-    torch.cuda.synchronize()
-    kstats = profile.summary()
-    profile.enable(False)
+    if args.full:
+        torch.cuda.synchronize()
+        kstats = profile.summary()
+        profile.enable(False)
     use_graph = args.graph != "off"
     capture_s = None
     if use_graph:
@@ -321,6 +358,10 @@ def run_ns(args, dev):
     elapsed = time.perf_counter() - t0
     edges = tr.edges_total() - e0
     loss = float(tr.loss)
+    # what a caller of the step holds after it: the batch's loss, the gradients the backward left
+    # in p.grad (the rank sum after the exchange) and the parameters Adam stepped to
+    dump_outputs(args, {"loss": tr.loss, "params": tr.param_vector(),
+                        "grads": torch.cat([p.grad.detach().reshape(-1) for p in tr.params])})
     if world > 1:
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -371,8 +412,9 @@ def run_ns(args, dev):
             "aggregated_edges_per_step_per_rank": edges / world / args.steps,
             "final_loss": loss,
         },
-        "ns_kernels_ms": {k: round(v[1], 4) for k, v in kstats.items()},
     }
+    if args.full:
+        res["ns_kernels_ms"] = {k: round(v[1], 4) for k, v in kstats.items()}
     res["config"]["engine"] = "fused regnn_nsm_step" if tr.fused is not None else "module"
     if "nsm_step" in kstats and nsm_bytes:
         # the roofline of `value`'s own kernel: the fused model step (regnn_nsm_step), its
@@ -436,6 +478,16 @@ def build_full(args, dev, wl):
     gen = torch.Generator(device=dev)
     gen.manual_seed(2)
     torch.manual_seed(3)
+    # --dump-outputs: the step keeps what it returned to its caller (the layer's output and
+    # parameter gradients, or the loss) for outputs() after the last timed step
+    keep_last, last = bool(getattr(args, "dump_outputs", None)), {}
+
+    def _flat(ts):
+        return torch.cat([t.detach().reshape(-1) for t in ts if t is not None])
+
+    def layer_outputs():
+        return {"y": last["y"], "grads": _flat(last["grads"])}
+
     if wl in ("mag", "dblp"):
         if wl == "mag":
             gd = synth.mag_like(args.scale, seed=0, device=dev, zipf_s=args.zipf)
@@ -492,12 +544,14 @@ def build_full(args, dev, wl):
         def step():
             y = conv(g, x, e_feat)
             y.backward(gout)
+            if keep_last:
+                last["y"], last["grads"] = y.detach(), [p_.grad for p_ in params]
             for p_ in params:
                 p_.grad = None
 
         torch.cuda.synchronize()
         log(f"[bench] gat: N={gd['N']:,} E={rg.E:,} R={gd['R']} built in {time.time() - t0:.1f}s")
-        return dict(step=step, edges_per_step=rg.E, rg=rg, R=gd["R"],
+        return dict(step=step, outputs=layer_outputs, edges_per_step=rg.E, rg=rg, R=gd["R"],
                     kernels=("gat_fused_fwd", "spmm_heads_bwd", "gat_softmax_bwd",
                              "gat_attn_lse"), convs=1, N=rg.n_dst, E=rg.E, train_nodes=0)
     elif wl == "gatv2":
@@ -515,13 +569,15 @@ def build_full(args, dev, wl):
         def step():
             y = conv(g, x, e_feat)
             y.backward(gout)
+            if keep_last:
+                last["y"], last["grads"] = y.detach(), [p_.grad for p_ in params]
             for p_ in params:
                 p_.grad = None
 
         torch.cuda.synchronize()
         log(f"[bench] gatv2: N={gd['N']:,} E={rg.E:,} R={gd['R']} built in {time.time() - t0:.1f}s; "
             f"long rows csr={rg.csr_plan.n_long} csc={rg.csc_plan.n_long}")
-        return dict(step=step, edges_per_step=rg.E, rg=rg, R=gd["R"],
+        return dict(step=step, outputs=layer_outputs, edges_per_step=rg.E, rg=rg, R=gd["R"],
                     kernels=("gatv2_score_fwd", "gatv2_score_bwd", "edge_softmax_fwd",
                              "edge_softmax_bwd", "spmm_heads_fwd", "spmm_heads_bwd"),
                     convs=1, N=rg.n_dst, E=rg.E, train_nodes=0)
@@ -552,11 +608,17 @@ def build_full(args, dev, wl):
         if world > 1:
             mag.flat_grad_allreduce(params, world)      # replicas: averaged gradients
         opt.step()
+        if keep_last:
+            last["loss"], last["grads"] = loss.detach(), [p_.grad for p_ in params]
+
+    def train_outputs():
+        return {"loss": last["loss"], "grads": _flat(last["grads"]), "params": _flat(params)}
 
     torch.cuda.synchronize()
     log(f"[bench] {wl}: N={gd['N']:,} E={rg.E:,} R={gd['R']} built in {time.time() - t0:.1f}s; "
         f"long rows csr={rg.csr_plan.n_long} csc={rg.csc_plan.n_long}")
-    return dict(step=step, edges_per_step=convs * rg.E, rg=rg, R=gd["R"], kernels=kern,
+    return dict(step=step, outputs=train_outputs, edges_per_step=convs * rg.E, rg=rg, R=gd["R"],
+                kernels=kern,
                 convs=convs, N=rg.n_dst, E=rg.E, train_nodes=train_nodes)
 
 
@@ -598,7 +660,9 @@ def pmc_traffic_ns(args):
     return rec["nsm_step"]["bytes_per_launch"], "ok"
 
 
-def run_full(args, dev, wl):
+def run_full(args, dev, wl, dump=True):
+    """dump: this workload's step is the run's timed path (--dump-outputs writes its outputs);
+    False for the full_batch leg of an ns run, whose outputs are the NS step's."""
     from regnn_hip import profile
     rank, world = _world()
     w = build_full(args, dev, wl)
@@ -644,6 +708,8 @@ def run_full(args, dev, wl):
     if not use_graph:
         kstats = profile.summary()
         profile.enable(False)
+    if dump:
+        dump_outputs(args, w["outputs"]() if getattr(args, "dump_outputs", None) else {})
     edges = w["edges_per_step"] * args.steps
     if world > 1:
         t = torch.tensor([elapsed], device=dev)
@@ -809,9 +875,17 @@ def main():
                          "small graphs dblp/acm/imdb)")
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
                     help="feature storage type of the full-graph REGCN workloads (mag, dblp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the NS step's "
+                         "per-kernel times and rooflines (eager profiled steps), and at N=1 the "
+                         "full-graph roofline leg and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baselines")
     ap.add_argument("--no-full-batch", action="store_true",
-                    help="ns at N=1: skip the full-graph roofline leg")
+                    help="--full, ns at N=1: skip the full-graph roofline leg")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks as a child
@@ -824,11 +898,11 @@ def main():
         args.steps = 160 if args.workload == "ns" else 20
     if args.workload == "ns":
         result = run_ns(args, dev)
-        if world == 1 and not args.no_full_batch:
+        if args.full and world == 1 and not args.no_full_batch:
             # the full-graph REGraphConv step: north_star's SpMM roofline gate, under its own key
             if not explicit_steps:
                 args.steps = 20
-            result["full_batch"] = run_full(args, dev, "mag")
+            result["full_batch"] = run_full(args, dev, "mag", dump=False)
     elif args.workload == "ns_infer":
         result = run_other_ns_infer(args, dev)
     elif args.workload == "ns_epoch":
@@ -843,7 +917,7 @@ def main():
                           "random features/labels)",
                   "config": dict(fb["config"], parallelism=f"replicas x{world} (averaged grads)"),
                   "roofline": fb["roofline"], "kernels_ms": fb["kernels_ms"]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb, threads = cpu_baseline()
         mag_key = [k for k in cb if k.startswith("mag_like")][0]
         full = {
@@ -891,12 +965,15 @@ def run_other_ns_infer(args, dev):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    pred = None
     for _ in range(args.steps):
-        si.run(x_dict, gather="argmax")
+        pred = si.run(x_dict, gather="argmax")
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if pred is not None:
+        dump_outputs(args, {"pred": pred})
     if world > 1:
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -80,10 +80,22 @@ class Guard:
             rank = self.dist.get_rank() if self.dist.is_initialized() else -1
             print(f"[rank {rank}] the agreement after '{what}' failed: {e}", file=sys.stderr,
                   flush=True)
+            self._drop_broken_gloo_group()
             raise RankFailure(what, -1, e) from e
         if n_bad:
             raise RankFailure(what, n_bad)
         return True
+
+    def _drop_broken_gloo_group(self):
+        """a gloo group whose collective failed (its peer died) is destroyed here, before the
+        exit: left to the interpreter's shutdown, its transport threads are at times still
+        joinable when the group is freed, and the process then ends in std::terminate (SIGABRT)
+        instead of EXIT_CODE. RCCL groups are left as they are."""
+        try:
+            if self.dist.is_initialized() and self.dist.get_backend() == "gloo":
+                self.dist.destroy_process_group()
+        except Exception:                    # noqa: BLE001 (the exit code is what matters now)
+            traceback.print_exc()
 
     def stage(self, what, fn, always=None):
         if self.world <= 1:

@@ -728,10 +728,40 @@ def gen_regnn_init():
     save("mag_regnn_init", dict(configs=meta), st)
 
 
+# ------------------------------------------------------------------------------------------
+# parameter layouts of model/*.py (names and shapes; tests/test_cpu_dropin.py)
+# ------------------------------------------------------------------------------------------
+def gen_layouts():
+    _purge(["dgl", "layer", "model", "utils"])
+    _use_paths([SHIM, REF])
+    import dgl
+    import torch.nn.functional as F
+    g = dgl.DGLGraph(([0, 1], [1, 0]), num_nodes=2)
+    dims = [12, 7]
+    cases = {
+        "REGCN": dict(args=[10, 100.0, 64, 64, 4, 3, "elu", 0.5, dims], kwargs={}),
+        "REGAT": dict(args=[10, 100.0, 2, 32, 32, 4, [8, 8, 1], "elu", 0.5, 0.5, 0.01, False,
+                            dims], kwargs={}),
+        "REMixHop": dict(args=[10, 100.0, 64, 64, 4, 2, dims],
+                         kwargs=dict(input_dropout=0.5, activation="elu")),
+    }
+    for name, c in cases.items():
+        cls = getattr(importlib.import_module("model." + name), name)
+        net = cls(g, *[F.elu if a == "elu" else a for a in c["args"]],
+                  **{k: F.elu if v == "elu" else v for k, v in c["kwargs"].items()})
+        c["layout"] = {n: list(p.shape) for n, p in net.named_parameters()}
+        c["layer_modules"] = sorted({type(m).__module__ for m in net.modules()
+                                     if type(m).__module__.startswith("layer.")})
+    with open(os.path.join(HERE, "model_layouts.json"), "w") as f:
+        json.dump(cases, f, indent=1)
+        f.write("\n")
+    print("model_layouts.json:", {k: len(c["layout"]) for k, c in cases.items()})
+
+
 if __name__ == "__main__":
     torch.set_default_dtype(torch.float64)
     which = sys.argv[1:] or ["layers", "models", "mag", "extra", "maggat", "regnn", "schema",
-                             "ft5", "init"]
+                             "ft5", "init", "layouts"]
     if "layers" in which:
         gen_layers()
     if "models" in which:
@@ -750,3 +780,5 @@ if __name__ == "__main__":
         gen_regnn_ft5()
     if "init" in which:
         gen_regnn_init()
+    if "layouts" in which:
+        gen_layouts()

@@ -1,57 +1,42 @@
-"""Drop-in check in THIS container (skipped where /root/reference is absent, e.g. the GPU box):
-the reference's own model/REGCN.py, model/REGAT.py and model/REMixHop.py import and construct on
-this build's ``layer`` + ``dgl`` packages and produce the same parameter layout as the build's
-nets. (Forward needs a ROCm device; parity of forward/backward is covered by the GPU tests on
-golden vectors generated from these same reference files.)"""
-import importlib
+"""Drop-in check of the parameter layout: this build's nets (regnn_hip.nets REGCN / REGAT /
+REMixHop on the build's ``layer`` + ``dgl`` packages) carry the names and shapes the reference's
+own model/REGCN.py, model/REGAT.py and model/REMixHop.py do, so a reference ``state_dict`` loads
+unchanged. The reference's layouts are recorded data (tests/golden/model_layouts.json, written
+by tests/golden/make_golden.py from the reference's model files with the constructor arguments
+stored beside them). (Forward needs a ROCm device; parity of forward/backward is covered by the
+GPU tests on golden vectors generated from these same reference files.)"""
+import json
 import os
-import sys
 
-import pytest
 import torch.nn.functional as F
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "model")),
-                                reason="reference checkout not present")
-
-
-def _import_ref_models():
-    saved = dict(sys.modules)
-    for k in list(sys.modules):
-        if k == "model" or k.startswith("model."):
-            del sys.modules[k]
-    sys.path.insert(1, REF)        # after re-gnn_amd (conftest puts it first): our layer/dgl win
-    try:
-        import layer
-        assert "re-gnn_amd" in layer.__file__
-        return (importlib.import_module("model.REGCN").REGCN,
-                importlib.import_module("model.REGAT").REGAT,
-                importlib.import_module("model.REMixHop").REMixHop)
-    finally:
-        sys.path.remove(REF)
-        for k in list(sys.modules):
-            if (k == "model" or k.startswith("model.")) and k not in saved:
-                del sys.modules[k]
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _layout(m):
-    return {n: tuple(p.shape) for n, p in m.named_parameters()}
+    return {n: list(p.shape) for n, p in m.named_parameters()}
+
+
+def _arg(a):
+    return F.elu if a == "elu" else a
 
 
 def test_reference_models_construct_on_build():
     import dgl
+    import layer
     from regnn_hip import nets
-    RREGCN, RREGAT, RREMixHop = _import_ref_models()
+    assert "re-gnn_amd" in layer.__file__
+    with open(os.path.join(HERE, "golden", "model_layouts.json")) as f:
+        cases = json.load(f)
+    assert sorted(cases) == ["REGAT", "REGCN", "REMixHop"]
     g = dgl.DGLGraph(([0, 1], [1, 0]), num_nodes=2)
-    dims = [12, 7]
-    a = RREGCN(g, 10, 100.0, 64, 64, 4, 3, F.elu, 0.5, dims)
-    b = nets.REGCN(g, 10, 100.0, 64, 64, 4, 3, F.elu, 0.5, dims)
-    assert _layout(a) == _layout(b)
-    a = RREGAT(g, 10, 100.0, 2, 32, 32, 4, [8, 8, 1], F.elu, 0.5, 0.5, 0.01, False, dims)
-    b = nets.REGAT(g, 10, 100.0, 2, 32, 32, 4, [8, 8, 1], F.elu, 0.5, 0.5, 0.01, False, dims)
-    assert _layout(a) == _layout(b)
-    a = RREMixHop(g, 10, 100.0, 64, 64, 4, 2, dims, input_dropout=0.5, activation=F.elu)
-    b = nets.REMixHop(g, 10, 100.0, 64, 64, 4, 2, dims, input_dropout=0.5, activation=F.elu)
-    assert _layout(a) == _layout(b)
-    # the reference model's layers ARE this build's classes
-    assert type(a.layers[0]).__module__ == "layer.REMixHopConv"
+    for name, c in cases.items():
+        b = getattr(nets, name)(g, *[_arg(a) for a in c["args"]],
+                                **{k: _arg(v) for k, v in c["kwargs"].items()})
+        assert _layout(b) == c["layout"], name
+        assert len(c["layout"]) > 0
+        # the model's layers are this build's classes, under the reference's module names
+        mods = sorted({type(m).__module__ for m in b.modules()
+                       if type(m).__module__.startswith("layer.")})
+        assert mods == c["layer_modules"], name
+    assert cases["REMixHop"]["layer_modules"] == ["layer.REMixHopConv"]

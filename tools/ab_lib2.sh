@@ -1,13 +1,13 @@
 #!/bin/bash
 # A/B of library builds on the NS bench: tools/ab_lib2.sh REPS lib1 lib2 ... ("cur" = the in-tree
-# library), interleaved, 300 timed steps each
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out
+# library), interleaved, 300 timed steps each; logs under $REGNN_OUT (default bench_out/)
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp && OUT=${REGNN_OUT:-bench_out} && mkdir -p $OUT
 reps=$1; shift 1
 for r in $(seq $reps); do
   for lib in "$@"; do
     if [ "$lib" = cur ]; then unset REGNN_LIB; else export REGNN_LIB=$PWD/ab/libregnn_$lib.so; fi
-    timeout -k 10 200 python bench.py --workload ns --no-full-batch --no-cpu-baseline --steps 300 ${AB_ARGS} > gpurun_out/ab.log 2>&1 || { tail -5 gpurun_out/ab.log; exit 1; }
-    echo "$lib $(grep '^{' gpurun_out/ab.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step"]*1000,1), "us", round(d["value"]/1e6,1), "M", d["ns_kernels_ms"])')"
+    timeout -k 10 200 python bench.py --full --workload ns --no-full-batch --no-cpu-baseline --steps 300 ${AB_ARGS} > $OUT/ab.log 2>&1 || { tail -5 $OUT/ab.log; exit 1; }
+    echo "$lib $(grep '^{' $OUT/ab.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step"]*1000,1), "us", round(d["value"]/1e6,1), "M", d["ns_kernels_ms"])')"
   done
 done
 unset REGNN_LIB
