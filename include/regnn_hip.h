@@ -41,7 +41,7 @@ enum { REGNN_F32 = 0, REGNN_BF16 = 1 };
  * <rows, gx_raw> / out_scale (out_scale > 0). Not combinable with edge_grad or the _next call. */
 enum { REGNN_SELF_PRESCALED = 0x100 };
 
-/* ABI version (bumped on any signature or semantics change; currently 46). */
+/* ABI version (bumped on any signature or semantics change; currently 47). */
 int regnn_abi_version(void);
 
 /* Tuning knob (process-wide, for A/B measurements; defaults are the shipped configuration).
@@ -662,7 +662,8 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
 /* The fused step's outer (meta-only, strided) hop with layer 0's parameter-free input sums
  * (relation slots: each (target type, source type) pair has one relation). Samples hop `hop` as
  * regnn_ns_hop(meta_only = 1, strided = 1) does -- the same slots, scnt, inv, blk_rel, edge_type /
- * edge_off, sizes[hop + 1] = sizes[hop], edge counts into sizes[8 + hop] and state[5] -- and then
+ * edge_off (the last three optional, below), sizes[hop + 1] = sizes[hop], edge counts into
+ * sizes[8 + hop] and state[5] -- and then
  * sums each row i's sampled raw input rows (tables[t] rows local[u], K = 128 fp32) per source node
  * type: s_agg[i][t][:] = sum of the rows of type t (unweighted), s_w[i][t] = their count,
  * u_self[i][:] = the self loop's row, u_rel[i][t] = the relation of type t's edges (-1: none),
@@ -687,13 +688,30 @@ typedef struct regnn_ns_csc_job {
     int32_t* csc_ent;
     int32_t* csc_long;
 } regnn_ns_csc_job;
+/* layout (may be NULL; ABI 47): node ids grouped by type -- type t's nodes are the ids
+ * [type_off[t], type_off[t + 1]) (equal offsets: a type without nodes), node u's table row is
+ * u - type_off[type(u)], and every edge from a node of type s into a node of type d has the
+ * relation pair_rel[d][s] (-1: the graph has no such edge). The caller has checked all three
+ * against its graph (regnn_hip.ns.type_layout). With a layout a slot's source type, table row and
+ * relation are computed from its node id: etype / ntype / local are not read and may be NULL; the
+ * outputs are the same bits. The struct is read on the host during the call (a captured graph
+ * holds its values). REGNN_EINVAL: n_types differs from the call's, type_off[0] != 0, offsets
+ * that decrease, a relation outside [-1, num_edge_types).
+ * blk_rel / edge_type / edge_off (ABI 47): all three NULL skips the per-slot meta writes (nothing
+ * reads them when the sums are what layer 0 consumes); one or two NULL is REGNN_EINVAL. */
+typedef struct regnn_ns_type_layout {
+    int32_t n_types;            /* T in [1, 4], the call's n_types */
+    int64_t type_off[5];        /* type_off[0] = 0 <= .. <= type_off[T] = nodes (< 2^31 - 1) */
+    int32_t pair_rel[4][4];     /* [target type][source type] -> edge relation, -1: none */
+} regnn_ns_type_layout;
 int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                             const int32_t* ntype, int32_t num_edge_types, int32_t k, int32_t hop,
                             int64_t* state, int32_t* sizes, const int32_t* n_id, int32_t cap_dst,
                             int32_t* scnt, uint8_t* blk_rel, float* inv, const int64_t* local,
                             int32_t* edge_type, int64_t* edge_off, const float* const* tables,
                             int32_t n_types, int32_t K, float* s_agg, float* s_w, float* u_self,
-                            int32_t* u_rel, const regnn_ns_csc_job* csc, hipStream_t stream);
+                            int32_t* u_rel, const regnn_ns_csc_job* csc,
+                            const regnn_ns_type_layout* layout, hipStream_t stream);
 
 /* Backward of a sampled block's aggregation y[v] = out_scale[v] sum_e rel_table[rel_e] x[idx_e]
  * (+ bias) over rows v < n_rows (the forward is regnn_spmm_fwd on the block):

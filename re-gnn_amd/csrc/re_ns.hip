@@ -914,7 +914,25 @@ struct NsSumArgs {
     const float* xt[8]; int T;
     float* s_agg; float* s_w; float* u_self; int32_t* u_rel;
     NsCscJob csc; int csc_blocks;          // an earlier hop's transposed index (csc_blocks > 0)
+    // DERIVE (node ids grouped by type, regnn_ns_type_layout): type q's first node id (q = 1..3;
+    // INT_MAX past the last type) and, per target type, a byte per source type: the pair's
+    // relation (0xFF: none). By value, so a captured graph holds them
+    int toff[4]; uint32_t pair[4];
 };
+
+// node u's type from the type offsets (scalar registers): empty types (equal offsets) are skipped
+__device__ __forceinline__ int ns_type_of(const NsSumArgs& A, int u) {
+    return (u >= A.toff[1] ? 1 : 0) + (u >= A.toff[2] ? 1 : 0) + (u >= A.toff[3] ? 1 : 0);
+}
+
+// type t's first node id (a node's table row is its id minus this)
+__device__ __forceinline__ int ns_type_first(const NsSumArgs& A, int t) {
+    int o = 0;
+#pragma unroll
+    for (int q = 1; q < 4; ++q)
+        if (t == q) o = A.toff[q];
+    return o;
+}
 
 template <int NT>
 __device__ __forceinline__ const float* pick_tab(const NsSumArgs& A, int t) {
@@ -938,7 +956,11 @@ constexpr int kNsSumOcc = REGNN_NS_SUM_UN32 > 11 ? 3 : 4;   // waves per SIMD th
 constexpr int kNsSumWaves = 4;             // waves per block (256 threads: they fit beside the
                                            // model's kernels on a shared CU)
 
-template <int G, int NT>
+// DERIVE: a slot's source type, table row and relation come from its node id, the type offsets
+// and the pair table (no etype / ntype / local loads: three random line transactions per slot
+// and one level of the dependent chain less); the same values, so the same bits in every output.
+// The per-slot meta (blk_rel / e_type / e_off) is written only when blk_rel is not NULL
+template <int G, int NT, bool DERIVE>
 __global__ void __launch_bounds__(64 * kNsSumWaves, kNsSumOcc)
 ns_sample_sums_kernel(NsSumArgs A) {
     // the first csc_blocks workgroups build the earlier hop's transposed index (latency-bound:
@@ -997,29 +1019,58 @@ ns_sample_sums_kernel(NsSumArgs A) {
         }
         // this lane's draw: a sampled edge (lane < cnt)
         int my_t = 0, my_lo = 0, my_r = 0;     // table rows < 2^31 (checked by the host)
+        const bool meta = A.blk_rel != nullptr;
+        int tt0 = 0;                           // DERIVE: the target row's type and pair word
+        uint32_t pw = 0;
+        if constexpr (DERIVE) {
+            tt0 = ns_type_of(A, t);
+            pw = A.pair[0];
+#pragma unroll
+            for (int q = 1; q < 4; ++q)
+                if (tt0 == q) pw = A.pair[q];
+        }
         if (lane < cnt) {
             const int p = b + slot;
             const int u = A.idx[p];
             const int64_t bp = base + rank;
-            my_r = A.etype[p];
-            my_t = A.ntype[u];
-            const int64_t lo = A.local[u];
-            my_lo = int(lo);
-            A.blk_rel[bp] = uint8_t(my_r);
-            A.e_type[bp] = my_t;
-            A.e_off[bp] = lo;
+            int64_t lo;
+            if constexpr (DERIVE) {
+                my_t = ns_type_of(A, u);
+                my_lo = u - ns_type_first(A, my_t);
+                my_r = int((pw >> (8 * my_t)) & 0xFFu);
+                lo = my_lo;
+            } else {
+                my_r = A.etype[p];
+                my_t = A.ntype[u];
+                lo = A.local[u];
+                my_lo = int(lo);
+            }
+            if (meta) {
+                A.blk_rel[bp] = uint8_t(my_r);
+                A.e_type[bp] = my_t;
+                A.e_off[bp] = lo;
+            }
         }
         // slot order: lane j < cnt takes slot j's entry, lane cnt the self loop
         int st = __shfl(my_t, src, G), sr = __shfl(my_r, src, G), slo = __shfl(my_lo, src, G);
         if (lane == cnt) {
             const int64_t bp = base + cnt;
-            st = A.ntype[t];
+            int64_t lo;
+            if constexpr (DERIVE) {
+                st = tt0;
+                slo = t - ns_type_first(A, tt0);
+                lo = slo;
+            } else {
+                st = A.ntype[t];
+                lo = A.local[t];
+                slo = int(lo);
+            }
             sr = A.n_et + st;
-            const int64_t lo = A.local[t];
-            slo = int(lo);
-            A.blk_rel[bp] = uint8_t(sr);
-            A.e_type[bp] = st;
-            A.e_off[bp] = lo;
+            if (meta) {
+                A.blk_rel[bp] = uint8_t(sr);
+                A.e_type[bp] = st;
+                A.e_off[bp] = lo;
+            }
         }
         if (lane == 0) {
             A.scnt[i] = cnt;
@@ -1865,11 +1916,33 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
                             int32_t* scnt, uint8_t* blk_rel, float* inv, const int64_t* local,
                             int32_t* edge_type, int64_t* edge_off, const float* const* tables,
                             int32_t n_types, int32_t K, float* s_agg, float* s_w, float* u_self,
-                            int32_t* u_rel, const regnn_ns_csc_job* csc, hipStream_t stream) {
-    if (!ptr || !idx || !etype || !ntype || !state || !sizes || !n_id || !scnt || !blk_rel ||
-        !inv || !local || !edge_type || !edge_off || !tables || !s_agg || !s_w || !u_self ||
-        !u_rel || cap_dst <= 0 || hop < 0 || hop > 6 || num_edge_types < 0)
+                            int32_t* u_rel, const regnn_ns_csc_job* csc,
+                            const regnn_ns_type_layout* layout, hipStream_t stream) {
+    if (!ptr || !idx || !state || !sizes || !n_id || !scnt || !inv || !tables || !s_agg ||
+        !s_w || !u_self || !u_rel || cap_dst <= 0 || hop < 0 || hop > 6 || num_edge_types < 0)
         return REGNN_EINVAL;
+    // the lookup tables: read without a layout only
+    if (!layout && (!etype || !ntype || !local)) return REGNN_EINVAL;
+    // the per-slot meta: all three outputs or none
+    if ((blk_rel || edge_type || edge_off) && !(blk_rel && edge_type && edge_off))
+        return REGNN_EINVAL;
+    int toff[4] = {0, INT32_MAX, INT32_MAX, INT32_MAX};
+    uint32_t pair[4] = {~0u, ~0u, ~0u, ~0u};
+    if (layout) {
+        if (layout->n_types != n_types || n_types < 1 || n_types > 4 || layout->type_off[0] != 0)
+            return REGNN_EINVAL;
+        for (int t = 0; t < n_types; ++t)
+            if (layout->type_off[t + 1] < layout->type_off[t]) return REGNN_EINVAL;
+        for (int a = 0; a < n_types; ++a)
+            for (int b = 0; b < n_types; ++b) {
+                const int r = layout->pair_rel[a][b];
+                if (r < -1 || r >= num_edge_types) return REGNN_EINVAL;
+                if (r > 254) return REGNN_EUNSUPPORTED;        // a byte per pair, 0xFF: none
+                if (r >= 0) pair[a] = (pair[a] & ~(0xFFu << (8 * b))) | (uint32_t(r) << (8 * b));
+            }
+        if (layout->type_off[n_types] >= INT32_MAX) return REGNN_EUNSUPPORTED;   // int32 node ids
+        for (int t = 1; t < n_types; ++t) toff[t] = int(layout->type_off[t]);
+    }
     if (K != kNsSumK || n_types < 1 || n_types > 4 || k < 1 || k > 63) return REGNN_EUNSUPPORTED;
     if (int64_t(cap_dst) * (k + 1) >= (int64_t(1) << 31)) return REGNN_EUNSUPPORTED;
     NsSumArgs A{};
@@ -1877,6 +1950,10 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
     A.n_et = num_edge_types; A.n_id = n_id; A.sizes = sizes; A.hop = hop; A.cap = cap_dst;
     A.k = k; A.state = state; A.scnt = scnt; A.blk_rel = blk_rel; A.inv = inv;
     A.e_type = edge_type; A.e_off = edge_off; A.T = n_types;
+    for (int q = 0; q < 4; ++q) {
+        A.toff[q] = toff[q];
+        A.pair[q] = pair[q];
+    }
     for (int t = 0; t < n_types; ++t) {
         if (!tables[t] || reinterpret_cast<uintptr_t>(tables[t]) % 16) return REGNN_EINVAL;
         A.xt[t] = tables[t];
@@ -1896,19 +1973,46 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
                          csc->csc_long};
         A.csc_blocks = csc_blocks(csc->cap_e);
     }
-    static const int sum_blocks = [] {     // REGNN_NS_SUM_BLOCKS: cap the grid (0: a row per lane group)
+    // REGNN_NS_SUM_BLOCKS: N > 0 caps the grid at N blocks, < 0: a block per row group whatever
+    // their number; 0 / unset: no more blocks than the GPU holds at once, each taking the same
+    // number of row groups (mag-10x, 13312 rows = 1664 groups on 1024 resident blocks: 832 blocks
+    // of two rounds; 1664 blocks ran as 1.6 waves of blocks whose second wave displaced the
+    // model's kernels: 103.7-104.2 against 99.4-99.8 us per step, 6 x 160 steps interleaved)
+    static const int sum_blocks = [] {
         const char* v = getenv("REGNN_NS_SUM_BLOCKS");
         return v ? atoi(v) : 0;
     }();
+    static const int resident = [] {       // blocks of this kernel the GPU holds at once
+        int dev = 0, n_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            n_cu <= 0)
+            n_cu = 256;
+        return n_cu * (4 * kNsSumOcc / kNsSumWaves);
+    }();
     auto grid = [&](int rows_per_block) {
         const int g = (cap_dst + rows_per_block - 1) / rows_per_block;
-        return dim3(unsigned(A.csc_blocks + (sum_blocks > 0 && sum_blocks < g ? sum_blocks : g)));
+        int nb = g;
+        if (sum_blocks > 0) {
+            nb = sum_blocks < g ? sum_blocks : g;
+        } else if (sum_blocks == 0 && g > resident) {
+            const int rounds = (g + resident - 1) / resident;
+            nb = (g + rounds - 1) / rounds;
+        }
+        return dim3(unsigned(A.csc_blocks + nb));
     };
-    if (k + 1 <= 32)                   // two rows per wave (32 lanes each): sums in slot order
-        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4>), grid(2 * kNsSumWaves),
+    const bool derive = layout != nullptr;
+    if (k + 1 <= 32 && derive)         // two rows per wave (32 lanes each): sums in slot order
+        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, true>), grid(2 * kNsSumWaves),
+                           dim3(64 * kNsSumWaves), 0, stream, A);
+    else if (k + 1 <= 32)
+        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, false>), grid(2 * kNsSumWaves),
+                           dim3(64 * kNsSumWaves), 0, stream, A);
+    else if (derive)
+        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, true>), grid(kNsSumWaves),
                            dim3(64 * kNsSumWaves), 0, stream, A);
     else
-        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4>), grid(kNsSumWaves),
+        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, false>), grid(kNsSumWaves),
                            dim3(64 * kNsSumWaves), 0, stream, A);
     REGNN_LAUNCH_CHECK();
     return REGNN_OK;

@@ -215,18 +215,25 @@ class DeviceSampler:
                 if before_sums is not None:
                     before_sums()
                 ts = self.typed_sums[h]
-                et, eo = self.edge_meta[h]
+                # the graph's type layout (sampler_type_layout): the launch computes each slot's
+                # type / table row / relation; and the per-slot meta only where something may
+                # read it (ts["meta_unread"]: this hop's consumer reads the sums alone)
+                lay = ts.get("layout")
+                mode = SUMS_META["mode"]
+                skip = (lay is not None and ts.get("meta_unread", False) and mode != "on" and
+                        (mode == "off" or torch.cuda.is_current_stream_capturing()))
+                rel, et, eo = (None, None, None) if skip else (blk.rel, *self.edge_meta[h])
                 with timed("ns_typed_sums"):
                     L.call("regnn_ns_hop_typed_sums", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
                            L.ptr(self.etype_csr), L.ptr(self.ntype), self.num_edge_types, k, h,
                            L.ptr(self.state), L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h],
-                           L.ptr(b["scnt"]), L.ptr(blk.rel), L.ptr(blk.inv), L.ptr(self.local),
+                           L.ptr(b["scnt"]), L.ptr(rel), L.ptr(blk.inv), L.ptr(self.local),
                            L.ptr(et), L.ptr(eo), ts["tables"], ts["T"], ts["K"],
                            L.ptr(ts["s_agg"]), L.ptr(ts["s_w"]), L.ptr(ts["u_self"]),
                            L.ptr(ts["u_rel"]),
                            ctypes.addressof(self._csc_job(h - 1)) if deferred == h - 1 else None,
-                           L.stream())
-                self.meta_fresh[h] = True
+                           None if lay is None else ctypes.addressof(lay), L.stream())
+                self.meta_fresh[h] = not skip
                 self.sums_fresh[h] = True
                 continue
             self.sums_fresh[h] = False
@@ -557,33 +564,129 @@ PRE_SUMS = {"mode": os.environ.get("REGNN_NS_PRE_SUMS", "on")}
 GROUP_ORDER = {"mode": os.environ.get("REGNN_NS_GROUP_ORDER", "model")}
 
 
+# "on": where the graph's node ids are grouped by type (type_layout below), the sampler's sums
+# launch computes each slot's source type, table row and relation from its node id instead of
+# loading them from the per-edge / per-node tables (regnn_ns_type_layout); "off": the tables (A/B)
+TYPE_LAYOUT = {"mode": os.environ.get("REGNN_NS_TYPE_LAYOUT", "on")}
+# the sums launch's per-slot meta (blk_rel, edge_type, edge_off) once layer 0 reads the sums
+# instead: "auto" (default): written by eager calls (a caller may inspect the block between
+# steps), left out while a graph is captured (nothing in a replayed step reads them); "on" /
+# "off": always / never written (never: only with the type layout)
+SUMS_META = {"mode": os.environ.get("REGNN_NS_SUMS_META", "auto")}
+
+
+def pair_relations(node_type, csr_ptr, csr_idx, etype_csr, T):
+    """one pass over a graph's edges (CSR by target; plain tensors on any device): the [T, T]
+    int64 table (target type, source type) -> the pair's edge relation, -1 where the graph has no
+    such edge, and whether every pair has at most one relation (a pair with several keeps -1).
+    Edges at a node whose type lies outside [0, T) are left out."""
+    dev = csr_ptr.device
+    ptr = csr_ptr.to(torch.int64)
+    E = int(csr_idx.numel())
+    present = torch.zeros(_MT * _MT * 256, dtype=torch.bool, device=dev)
+    step = 1 << 26
+    for a in range(0, E, step):
+        b = min(E, a + step)
+        pos = torch.arange(a, b, device=dev)
+        dst = torch.searchsorted(ptr, pos, right=True) - 1
+        st = node_type[csr_idx[a:b].to(torch.int64)].to(torch.int64)
+        dt = node_type[dst].to(torch.int64)
+        r = etype_csr[a:b].to(torch.int64)
+        ok = (st >= 0) & (st < T) & (dt >= 0) & (dt < T)
+        present[((dt * _MT + st) * 256 + r)[ok]] = True
+    present = present.view(_MT, _MT, 256)[:T, :T]
+    per_pair = present.sum(2)
+    single = bool((per_pair <= 1).all().item())
+    rel = torch.where(per_pair == 1, present.to(torch.float32).argmax(2),
+                      torch.full_like(per_pair, -1))
+    return rel.cpu(), single
+
+
+def _pair_table(sampler, T):
+    """pair_relations of the sampler's graph, cached on the graph."""
+    rg = sampler.rg
+    key = ("_regnn_rel_slots", sampler.num_edge_types, T)
+    cache = getattr(rg, "_regnn_rel_slots", None)
+    if cache is None or cache[0] != key:
+        rel, ok = pair_relations(sampler.ntype, rg.csr_ptr, rg.csr_idx, sampler.etype_csr, T)
+        cache = rg._regnn_rel_slots = (key, ok, rel)
+    return cache
+
+
 def relation_slots_ok(sampler, T):
     """regnn_nsm_params.rel_slots: True when every (target type, source type) pair of the graph
     has at most one edge relation (ogbn-mag's typed relations: each edge type joins one source
     type to one target type), so layer 0 may sum its input rows per source type unweighted.
     One pass over the graph's edges, cached on the graph."""
+    return _pair_table(sampler, T)[1]
+
+
+def type_layout(node_type, local_node_idx, csr_ptr, csr_idx, etype_csr, T, pairs=None):
+    """The graph's type layout (regnn_ns_type_layout), or None when the graph has none: node ids
+    grouped by type, as the reference's preprocessing leaves them (mag/regnn_ns.py:141-142).
+    Plain tensors on any device. The layout holds when
+      * node_type is non-decreasing with values in [0, T), T <= 4 (a type without nodes is fine:
+        its offsets are equal and no id falls between them),
+      * local_node_idx[u] == u - off[node_type[u]] for every node (off: the types' first ids),
+      * every (target type, source type) pair of the edges has one relation (pairs: what
+        pair_relations returned for this graph, else computed here).
+    Returns dict(T, type_off = [0, .., nodes] (T + 1 ints), pair_rel = T x T lists, -1: none)."""
+    if T < 1 or T > 4:
+        return None
+    nt = node_type.reshape(-1).to(torch.int64)
+    lo = local_node_idx.reshape(-1).to(torch.int64)
+    n = int(nt.numel())
+    if n == 0 or lo.numel() != n or n >= 2 ** 31 - 1:
+        return None
+    if int(nt.min()) < 0 or int(nt.max()) >= T or bool((nt[1:] < nt[:-1]).any()):
+        return None
+    off = torch.zeros(T + 1, dtype=torch.int64, device=nt.device)
+    off[1:] = torch.cumsum(torch.bincount(nt, minlength=T), 0)
+    if not bool((lo == torch.arange(n, device=nt.device) - off[nt]).all()):
+        return None
+    rel, single = pairs if pairs is not None else pair_relations(nt, csr_ptr, csr_idx,
+                                                                 etype_csr, T)
+    if not single:
+        return None
+    return dict(T=T, type_off=[int(v) for v in off.cpu().tolist()],
+                pair_rel=[[int(v) for v in row] for row in rel.tolist()])
+
+
+class _NsTypeLayout(ctypes.Structure):
+    """regnn_ns_type_layout (include/regnn_hip.h)."""
+    _fields_ = [("n_types", ctypes.c_int32), ("type_off", ctypes.c_int64 * 5),
+                ("pair_rel", (ctypes.c_int32 * 4) * 4)]
+
+
+def layout_struct(lay):
+    """type_layout's dict as the C struct."""
+    s = _NsTypeLayout()
+    s.n_types = lay["T"]
+    for t, v in enumerate(lay["type_off"]):
+        s.type_off[t] = v
+    for a in range(4):
+        for b in range(4):
+            s.pair_rel[a][b] = lay["pair_rel"][a][b] if a < lay["T"] and b < lay["T"] else -1
+    return s
+
+
+def sampler_type_layout(sampler, T):
+    """the sampler's graph's regnn_ns_type_layout struct (TYPE_LAYOUT on, the graph has the
+    layout), else None; checked once per graph and cached on it as relation_slots_ok's verdict.
+    Needs the sampler's table rows (enable_edge_meta)."""
+    if TYPE_LAYOUT["mode"] == "off" or sampler.local is None:
+        return None
     rg = sampler.rg
-    key = ("_regnn_rel_slots", sampler.num_edge_types, T)
-    cache = getattr(rg, "_regnn_rel_slots", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    dev = rg.device
-    ptr = rg.csr_ptr.to(torch.int64)
-    present = torch.zeros(_MT * _MT * 256, dtype=torch.bool, device=dev)
-    step = 1 << 26
-    for a in range(0, rg.E, step):
-        b = min(rg.E, a + step)
-        pos = torch.arange(a, b, device=dev)
-        dst = torch.searchsorted(ptr, pos, right=True) - 1
-        st = sampler.ntype[rg.csr_idx[a:b].to(torch.int64)].to(torch.int64)
-        dt = sampler.ntype[dst].to(torch.int64)
-        r = sampler.etype_csr[a:b].to(torch.int64)
-        ok = (st >= 0) & (st < T) & (dt >= 0) & (dt < T)
-        present[((dt * _MT + st) * 256 + r)[ok]] = True
-    per_pair = present.view(_MT * _MT, 256).sum(1)
-    ok = bool((per_pair <= 1).all().item())
-    rg._regnn_rel_slots = (key, ok)
-    return ok
+    key = ("_regnn_type_layout", sampler.num_edge_types, T, sampler.local.data_ptr())
+    cache = getattr(rg, "_regnn_type_layout", None)
+    if cache is None or cache[0] != key:
+        _, ok, rel = _pair_table(sampler, T)
+        lay = type_layout(sampler.ntype, sampler.local, rg.csr_ptr, rg.csr_idx,
+                          sampler.etype_csr, T, pairs=(rel, ok))
+        # (the checked tensor is kept: its address cannot pass to another while the verdict lives)
+        cache = rg._regnn_type_layout = (key, None if lay is None else layout_struct(lay),
+                                         sampler.local)
+    return cache[1]
 
 
 class FusedStep:
@@ -703,7 +806,9 @@ class FusedStep:
             self._tables = (ctypes.c_void_p * T)(*[x_dict[k].data_ptr() for k in keys])
             sampler.typed_sums[nl - 1] = dict(
                 tables=self._tables, T=T, K=K, s_agg=self._buf(W.s_agg), s_w=self._buf(W.s_w),
-                u_self=self._buf(W.u_self), u_rel=self._buf(W.u_rel))
+                u_self=self._buf(W.u_self), u_rel=self._buf(W.u_rel),
+                # agg0 and bwd0 then read s_agg / s_w / u_self / u_rel only: not the hop's meta
+                layout=sampler_type_layout(sampler, T), meta_unread=True)
             W.pre_sums = 1
 
     def _buf(self, addr):
@@ -750,7 +855,8 @@ class FusedStep:
                 L.call("regnn_nsm_step", ctypes.addressof(self.P), ctypes.addressof(self.W),
                        torch.cuda.current_stream(self.device).cuda_stream)
             return
-        if not self.sampler.meta_fresh[self.n_layers - 1]:
+        # (with the sampler's sums the hop may leave the meta out: nothing of this step reads it)
+        if not self.W.pre_sums and not self.sampler.meta_fresh[self.n_layers - 1]:
             raise RuntimeError("run the sampler's hops after building FusedStep: layer 0 reads the "
                                "per-edge source type / table row they write")
         if self.W.pre_sums and not self.sampler.sums_fresh[self.n_layers - 1]:
@@ -1090,7 +1196,10 @@ class NSTrainer:
         urel = torch.full((cap, T + 1), -1, dtype=torch.int32, device=dev)
         ptrs = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tabs])
         s.typed_sums[last] = dict(tables=ptrs, T=T, K=K, s_agg=U, s_w=cnt, u_self=xself,
-                                  u_rel=urel, keep=tabs)
+                                  u_rel=urel, keep=tabs,
+                                  # ops.ns_slot_agg and its backward read U / cnt / xself / urel
+                                  # (and the block's inv) only: not the hop's per-slot meta
+                                  layout=sampler_type_layout(s, T), meta_unread=True)
         s.hop_strided[last] = True
         s.blocks[last].pre_sums = (U, cnt, xself, urel)
 
