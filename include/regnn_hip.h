@@ -41,7 +41,7 @@ enum { REGNN_F32 = 0, REGNN_BF16 = 1 };
  * <rows, gx_raw> / out_scale (out_scale > 0). Not combinable with edge_grad or the _next call. */
 enum { REGNN_SELF_PRESCALED = 0x100 };
 
-/* ABI version (bumped on any signature or semantics change; currently 47). */
+/* ABI version (bumped on any signature or semantics change; currently 48). */
 int regnn_abi_version(void);
 
 /* Tuning knob (process-wide, for A/B measurements; defaults are the shipped configuration).
@@ -642,7 +642,16 @@ int regnn_ns_batch(const int64_t* perm, int64_t n_perm, int32_t batch, int32_t r
  * the hop adds its edges to it and to state[5]. strided = 2 (with the transposed index, no
  * edge meta): everything but the transposed index and the sampled edges' blk_idx, which a
  * second call with strided = 3 and the same arguments then writes (on another stream if the
- * caller wants: nothing the next hop reads depends on it). */
+ * caller wants: nothing the next hop reads depends on it).
+ * csc_rank (ABI 48; may be NULL: the single launch above) [cap_e] int32, strided = 1 with the
+ * transposed index and no edge meta: the index in two launches, neither with a wait between
+ * workgroups -- the first resolves every slot's local source id, counts the sources' entries
+ * (csc_cnt) and stores each slot's rank in its source's segment (csc_rank); the second's
+ * workgroups (1024 slots each) all scan the counts by themselves and place their own slots at
+ * prefix[source] + rank, workgroup 0 also writing csc_ptr, the hub list and the piece table (the
+ * same values and layout; the error word is never raised). strided = 4 (needs csc_rank): the
+ * first of the two only -- csc_cnt / csc_rank / blk_idx final, csc_ptr / csc_ent / csc_long
+ * not written; regnn_nsm_step with csc_pending = 1 finishes the index beside its head. */
 #define REGNN_CSC_PIECE 1024
 #define REGNN_CSC_LONG_CAP (32768 / 17 + 1)          /* hub rows of a <= 32768-edge block */
 #define REGNN_CSC_LONG_NPIECE (REGNN_CSC_LONG_CAP + 1)
@@ -657,7 +666,8 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                  int32_t* blk_ptr, int32_t* blk_idx, uint8_t* blk_rel, int32_t* blk_pos,
                  int32_t* blk_row, float* inv, const int64_t* local, int32_t* edge_type,
                  int64_t* edge_off, int32_t meta_only, int32_t* csc_cnt, int32_t* csc_ptr,
-                 int32_t* csc_ent, int32_t* csc_long, int32_t strided, hipStream_t stream);
+                 int32_t* csc_ent, int32_t* csc_long, int32_t* csc_rank, int32_t strided,
+                 hipStream_t stream);
 
 /* The fused step's outer (meta-only, strided) hop with layer 0's parameter-free input sums
  * (relation slots: each (target type, source type) pair has one relation). Samples hop `hop` as
@@ -910,9 +920,9 @@ typedef struct regnn_nsm_work {
     float* p0;                /* cap[1] * 64: layer 0's group_input projection, summed per row */
     const struct regnn_nsm_adam* adam;   /* NULL, or the optimizer the last launch applies */
     float* gh1;               /* cap[0] * 64: G W_1^T of layer 1's target rows (its transposed pass) */
-    const int32_t* csc_ptr0;  /* hop 0's transposed index (regnn_ns_hop csc_ptr / csc_ent / */
-    const int32_t* csc_ent0;  /* csc_long) */
-    const int32_t* csc_long0;
+    int32_t* csc_ptr0;        /* hop 0's transposed index (regnn_ns_hop csc_ptr / csc_ent / */
+    int32_t* csc_ent0;        /* csc_long): read; written first when csc_pending */
+    int32_t* csc_long0;
     int32_t stride[REGNN_NSM_MAX_LAYERS];        /* per hop: 0 = CSR block, else its fixed stride */
     const int32_t* blk_cnt[REGNN_NSM_MAX_LAYERS]; /* per hop (strided): sampled edges per row */
     int32_t part;             /* two-layer step: 0 = every launch; 1 = the forward, the head and
@@ -935,6 +945,18 @@ typedef struct regnn_nsm_work {
                                  u_self / u_rel already hold the batch's layer-0 input sums
                                  (regnn_ns_hop_typed_sums): layer 0 reads them instead of
                                  gathering its input rows (ABI 41) */
+    /* ABI 48, two-layer step, strided hop 0: 1 = hop 0's regnn_ns_hop ran with strided = 4, so
+     * its index holds counts and ranks only; ceil(csc_cap_e / 1024) extra workgroups of the head's
+     * launch (idle CUs: the head has cap[0] / 16 workgroups) scan and place it, each by itself,
+     * and the gather reads it at the next launch boundary. Running it again over the same batch
+     * rewrites the same index. They form a second grid row (blockIdx.y = 1) of the head's
+     * launch, never wider than the head's own row. REGNN_EINVAL, before anything is launched:
+     * without the buffers or a strided hop 0, or when ceil(csc_cap_e / 1024) exceeds the head's
+     * ceil(cap[0] / 16) workgroups (stride[0] = 65 only; keep both halves in regnn_ns_hop). */
+    int32_t csc_pending;
+    int32_t csc_cap_e;             /* hop 0's slots: cap[0] * stride[0] <= 32768 */
+    const int32_t* csc_cnt0;       /* regnn_ns_hop's csc_cnt / csc_rank of hop 0 */
+    const int32_t* csc_rank0;
 } regnn_nsm_work;
 
 /* Adam over the flat parameter bucket whose gradient bucket starts at grad_base (every g_*

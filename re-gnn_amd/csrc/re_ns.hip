@@ -18,6 +18,8 @@
 // sampling of k distinct in-edge positions per target with hash(seed, t, j), ascending order;
 // n_id = targets, then new sources in first-seen order over the target-major edge list.
 #include "regnn_common.h"
+#include "re_csc_place.h"
+#include "re_nsm_common.h"
 
 #include <cstdlib>
 
@@ -892,6 +894,35 @@ __global__ void __launch_bounds__(kCscScanT)
 ns_resolve_csc_kernel(NsCscJob J, const int32_t* __restrict__ sizes,
                       const int64_t* __restrict__ state) {
     csc_resolve_place<16>(J, sizes, state, blockIdx.x, gridDim.x);
+}
+
+// The same index in two launches, neither with a wait between workgroups (ABI 48). First half:
+// every slot's local source id (as ns_resolve_kernel), the source's count and the slot's rank in
+// its source's segment (the counter's returned atomic: unspecified order, exact counts) -- the
+// only part that reads the dedup table the next batch's sampling overwrites. The second half
+// (csc_scan_place, re_csc_place.h) reads the slot's own buffers only.
+static_assert(kCscPlaceMax == kCscMax && kCscPlaceShort == kCscShort, "re_csc_place.h");
+__global__ void __launch_bounds__(kBlock)
+ns_csc_rank_kernel(const int32_t* __restrict__ gsrc, const uint64_t* __restrict__ g2l,
+                   int32_t* __restrict__ blk_idx, int32_t* __restrict__ csc_cnt,
+                   int32_t* __restrict__ csc_rank, int cap_e) {
+    const int bp = blockIdx.x * kBlock + threadIdx.x;
+    if (bp >= cap_e) return;
+    const int u = gsrc[bp];
+    if (u == -2) return;               // an empty slot of the strided layout
+    int lid;
+    if (u < 0) {                       // the self loop
+        lid = blk_idx[bp];
+    } else {
+        lid = int32_t(uint32_t(g2l[u]));
+        blk_idx[bp] = lid;
+    }
+    csc_rank[bp] = atomicAdd(csc_cnt + lid, 1);      // integer: exact in any order
+}
+
+__global__ void __launch_bounds__(kCscPlaceT) ns_csc_place_kernel(CscPlaceArgs A) {
+    extern __shared__ int csc_place_smem[];
+    csc_scan_place(A, blockIdx.x, csc_place_smem);
 }
 
 // The fused step's outer hop with layer 0's parameter-free input sums (relation slots): the
@@ -1803,7 +1834,8 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                  int32_t* blk_ptr, int32_t* blk_idx, uint8_t* blk_rel, int32_t* blk_pos,
                  int32_t* blk_row, float* inv, const int64_t* local, int32_t* edge_type,
                  int64_t* edge_off, int32_t meta_only, int32_t* csc_cnt, int32_t* csc_ptr,
-                 int32_t* csc_ent, int32_t* csc_long, int32_t strided, hipStream_t stream) {
+                 int32_t* csc_ent, int32_t* csc_long, int32_t* csc_rank, int32_t strided,
+                 hipStream_t stream) {
     if (!ptr || !idx || !etype || !ntype || !state || !sizes || !n_id || !g2l || !first ||
         !samp || !spos || !scnt || !gsrc || !flag || !tiles || !status || !blk_ptr || !blk_idx ||
         !blk_rel || !blk_pos || !blk_row || !inv || cap_dst <= 0 || hop < 0 || hop > 6 || num_edge_types < 0)
@@ -1820,6 +1852,8 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
     if (cap_e >= (int64_t(1) << 31)) return REGNN_EUNSUPPORTED;
     const int n_tiles = int((cap_e + kNsTile - 1) / kNsTile);
     if (csc && cap_e > kCscMax) return REGNN_EUNSUPPORTED;
+    // strided = 4: the split index's first half only (the caller's step finishes it)
+    if (strided == 4 && (!csc || !csc_rank || edge_type || lean)) return REGNN_EINVAL;
     if (strided == 3) {
         // the transposed index only (the part a strided = 2 call left out), on whatever stream
         // the caller runs it: resolve + counts + ranks, scan, placement
@@ -1856,6 +1890,24 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                            sizes, hop, state, g2l, first, status, n_id, ce);
         REGNN_LAUNCH_CHECK();
         if (csc && !edge_type && strided == 2) return REGNN_OK;   // the index: a strided = 3 call
+        if (csc && !edge_type && csc_rank) {
+            // the index in two launches without a wait between workgroups: counts + ranks, then
+            // every workgroup's own scan and placement (strided = 4: left to the caller's step)
+            hipLaunchKernelGGL(ns_csc_rank_kernel, dim3(unsigned((cap_e + kBlock - 1) / kBlock)),
+                               dim3(kBlock), 0, stream, gsrc, g2l, blk_idx, csc_cnt, csc_rank, ce);
+            REGNN_LAUNCH_CHECK();
+            if (strided == 4) return REGNN_OK;
+            const CscPlaceArgs P{sizes, hop, ce, k + 1, csc_cnt, csc_rank, blk_idx, blk_rel,
+                                 csc_ptr, csc_ent, csc_long};
+            const size_t lds = csc_place_lds(ce);
+            static size_t done = 0;
+            if (!nsm::set_lds(reinterpret_cast<const void*>(&ns_csc_place_kernel), lds, &done))
+                return REGNN_EUNSUPPORTED;
+            hipLaunchKernelGGL(ns_csc_place_kernel, dim3(unsigned(csc_place_blocks(ce))),
+                               dim3(kCscPlaceT), lds, stream, P);
+            REGNN_LAUNCH_CHECK();
+            return REGNN_OK;
+        }
         if (csc && !edge_type) {
             // the transposed index by many blocks in one launch: resolve + counts + ranks, the
             // last block's scan, every block's placement

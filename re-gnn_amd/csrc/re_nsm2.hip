@@ -26,6 +26,7 @@
 //   finalize  every gradient as a fixed-order sum of per-block partials; with an optimizer
 //             attached, Adam (regnn_adam_flat's arithmetic) on each element right after its sum.
 #include "re_nsm_common.h"
+#include "re_csc_place.h"
 
 #include <cstdlib>
 
@@ -759,6 +760,11 @@ struct HeadArgs {
     const float* w_out; const float* b_out; int C;
     float* gh; float* nvalid; float* part; int64_t part_w;
     float* g_rows; float* h_rows;          // [blocks * 16][C] softmax gradient, [blocks * 16][64] h
+    // the grid's second row (blockIdx.y = 1, launched only with regnn_nsm_work csc_pending)
+    // finishes hop 0's transposed index (csc_scan_place, re_csc_place.h) on CUs the head leaves
+    // idle; the gather reads it next. The row is told apart by a register, not by a kernel
+    // argument: a load ahead of the head's own first loads cost the step 3 us
+    CscPlaceArgs csc;
 };
 
 // o_w1 (the W_1 partial) starts on a 16-byte boundary: finalize sums it with float4 loads
@@ -789,6 +795,11 @@ static_assert(kHeadNQ == 4 && kHeadSL == 64, "step 4c / 4d sum four class parts;
 
 __global__ void __launch_bounds__(kHeadThreads, 1) head_kernel(HeadArgs A) {
     extern __shared__ float hl[];
+    if (__builtin_expect(blockIdx.y != 0, 0)) {    // block-uniform, ahead of every barrier
+        if (int(blockIdx.x) * kCscPlaceT < A.csc.cap_e)
+            csc_scan_place(A.csc, blockIdx.x, reinterpret_cast<int*>(hl));
+        return;
+    }
     const int C = A.C, CT = (C + 15) / 16, CP = head_cp(C);
     float* Wl = hl;                        // W_out image; after step 4: red [3][16][64]
     float* zs = Wl + head_wl(C);           // [16][CP]: z, then g
@@ -2173,6 +2184,18 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
     const bool split = w->split_finalize != 0;
     if (split && ad) return REGNN_EINVAL;
     const Slab2 S = slab2(p, w->cap[0]);
+    if (w->csc_pending && w->part != 2) {
+        // the index's second half rides in the head launch as a second grid row no wider than
+        // the head's own (a wider grid would add head workgroups past the slab): refused before
+        // anything is launched, the caller keeps both halves in regnn_ns_hop instead
+        const int ce = w->csc_cap_e;
+        if (!w->csc_cnt0 || !w->csc_rank0 || w->stride[0] <= 0 || ce <= 0 ||
+            ce > kCscPlaceMax || int64_t(w->cap[0]) * w->stride[0] != ce)
+            return REGNN_EINVAL;
+        if (csc_place_blocks(ce) > S.head_blocks) return REGNN_EINVAL;
+        const size_t hl = head_lds(C), pl = csc_place_lds(ce);
+        if ((hl > pl ? hl : pl) > size_t(160 * 1024 - 2560)) return REGNN_EUNSUPPORTED;
+    }
     const Drop drop = make_drop(p->p_drop);
     Ptrs lin_w{}, lin_b{}, xt{};
     for (int t = 0; t < T; ++t) {
@@ -2246,11 +2269,28 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         H.w_out = p->out_w; H.b_out = p->out_b; H.C = C;
         H.gh = w->gh1; H.nvalid = w->nvalid; H.part = w->slab + S.head; H.part_w = hw;
         H.g_rows = w->slab + S.hg; H.h_rows = w->slab + S.hh;
-        const size_t lds = head_lds(C);
+        size_t lds = head_lds(C);
+        int extra = 0;
+        if (w->csc_pending) {
+            // hop 0's index holds counts and ranks only (regnn_ns_hop strided = 4): finished by
+            // extra workgroups of this launch, under the head's own LDS limit
+            const int ce = w->csc_cap_e;
+            // (checked before the step's first launch, above)
+            H.csc = CscPlaceArgs{w->sizes, 0, ce, w->stride[0], w->csc_cnt0, w->csc_rank0,
+                                 w->blk_idx[0], w->blk_rel[0], w->csc_ptr0, w->csc_ent0,
+                                 w->csc_long0};
+            extra = csc_place_blocks(ce);
+            if (csc_place_lds(ce) > lds) lds = csc_place_lds(ce);
+        }
         static size_t done = 0;
         if (!set_lds(reinterpret_cast<const void*>(&head_kernel), lds, &done))
             return REGNN_EUNSUPPORTED;
-        hipLaunchKernelGGL(head_kernel, dim3(S.head_blocks), dim3(kHeadThreads), lds, stream, H);
+        // pending: a second grid row for the index (its blocks past `extra` leave at once). The
+        // row is never wider than the head's: extra <= head_blocks was checked above, so row 0
+        // holds exactly the head's workgroups, whose slab rows slab2() sized
+        static_assert(kHeadThreads == kCscPlaceT, "csc_scan_place runs on 1024 threads");
+        const dim3 grid(S.head_blocks, extra ? 2 : 1);
+        hipLaunchKernelGGL(head_kernel, grid, dim3(kHeadThreads), lds, stream, H);
         REGNN_LAUNCH_CHECK();
     }
     // 3. layer 1's transposed aggregation (a gather), layer 0's LayerNorm backward

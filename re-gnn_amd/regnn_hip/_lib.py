@@ -102,7 +102,7 @@ _SIG = {
     "regnn_ns_xent_fwd": ([P, P, P, P, I32, I32, I64, P, P, P, P, P, P], ctypes.c_int),
     "regnn_xent_bwd_colsum": ([P, P, P, P, P, I32, I32, I64, P, P, P], ctypes.c_int),
     "regnn_ns_hop": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P,
-                      P, P, P, P, P, P, I32, P, P, P, P, I32, P], ctypes.c_int),
+                      P, P, P, P, P, P, I32, P, P, P, P, P, I32, P], ctypes.c_int),
     "regnn_ns_hop_typed_sums": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P,
                                  I32, I32, P, P, P, P, P, P, P], ctypes.c_int),
     "regnn_ns_spmm_bwd": ([P, P, P, P, P, P, P, P, P, I32, I64, I32, P], ctypes.c_int),
@@ -137,7 +137,7 @@ for _name, (_args, _ret) in _SIG.items():
     _f.restype = _ret
 
 EXPORTED = tuple(_SIG)
-ABI_VERSION = 47
+ABI_VERSION = 48
 # (an A/B build of an older tree through REGNN_LIB may trail the ABI: a timing run only)
 if _so.regnn_abi_version() != ABI_VERSION and not os.environ.get("REGNN_LIB"):
     raise ImportError(f"regnn_hip: ABI mismatch ({_so.regnn_abi_version()} != {ABI_VERSION}); "

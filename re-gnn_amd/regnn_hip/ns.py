@@ -138,6 +138,12 @@ class DeviceSampler:
         # sums_fresh[h]: the latest run_hops wrote hop h's layer-0 input sums (typed_sums path)
         self.sums_fresh = [False] * len(self.sizes_k)
         self.csc = [None] * len(self.sizes_k)      # per hop: (cnt, ptr, ent, long) or None
+        # the split index build (CSC_SPLIT): per hop each slot's rank in its source's segment
+        self.csc_rank = [None] * len(self.sizes_k)
+        # csc_defer[h]: a strided hop h leaves its index's scan + placement to the fused step's
+        # head launch (FusedStep.defer_csc asks for it); csc_deferred[h]: the latest run_hops did
+        self.csc_defer = [False] * len(self.sizes_k)
+        self.csc_deferred = [False] * len(self.sizes_k)
         # strided: every hop's block in the fixed-stride layout (row i at i (k + 1), regnn_ns_hop
         # strided) -- the two-layer fused step's layout; False: the CSR layout the module path,
         # exact_adjs and the PyG-style API read
@@ -165,11 +171,14 @@ class DeviceSampler:
     def index_errors(self):
         """device int32 tensor: per hop the strided transposed index's sticky error word (1: a
         block of regnn_ns_hop's index launch gave up waiting for the publish and placed nothing;
-        the index of that batch is incomplete). Reading it is one host sync (check_index)."""
+        the index of that batch is incomplete). Reading it is one host sync (check_index). Only
+        the single-launch build (CSC_SPLIT off, CSC_FORK, CSC_FUSE) can raise it: the split
+        build's two launches have no wait between workgroups and never write the word."""
         return torch.stack([b["tiles"][-1] for b in self.hop_bufs])
 
     def check_index(self):
-        """raise if any hop's transposed index reported a failed build (index_errors)."""
+        """raise if any hop's transposed index reported a failed build (index_errors; the split
+        build, CSC_SPLIT, waits on nothing and cannot fail this way)."""
         bad = self.index_errors().cpu().tolist()
         if any(bad):
             raise RuntimeError(f"regnn_ns_hop: the transposed index build timed out waiting for "
@@ -183,7 +192,15 @@ class DeviceSampler:
             raise ValueError(f"the transposed index needs <= 32768 block edges, got {ce}")
         z = lambda n: torch.zeros(n, dtype=torch.int32, device=self.device)  # noqa: E731
         self.csc[hop] = (z(ce), z(ce + 1), z(ce), z(max(ce + 1, CSC_LONG_INTS)))
+        self.csc_rank[hop] = z(ce)
         return self.csc[hop]
+
+    def _csc_args(self, h, split):
+        """regnn_ns_hop's csc_cnt .. csc_rank of hop h (split: with the rank buffer, the
+        two-launch build)"""
+        c = self.csc[h]
+        args = [L.ptr(t) for t in c] if c is not None else [None] * 4
+        return args + [L.ptr(self.csc_rank[h]) if split and c is not None else None]
 
     # -- the per-step device work ------------------------------------------------------------
     def batch_from_perm(self, perm, rank=0, world=1):
@@ -237,8 +254,18 @@ class DeviceSampler:
                 self.sums_fresh[h] = True
                 continue
             self.sums_fresh[h] = False
+            # the split index build (counts + ranks, then scan + placement: regnn_ns_hop
+            # csc_rank): what a strided hop with an index and no edge meta runs unless the
+            # single-launch build is asked for (CSC_SPLIT off, or its CSC_FORK / CSC_FUSE forms);
+            # later: the second half left to the fused step's head launch (strided = 4)
+            later = bool(self.csc_defer[h] and sh and self.csc[h] is not None and
+                         self.edge_meta[h] is None and CSC_SPLIT["mode"] != "off")
+            fork = fork and not later
+            split = later or (CSC_SPLIT["mode"] != "off" and not fork and
+                              CSC_FUSE["mode"] == "off")
+            self.csc_deferred[h] = later
             # the transposed index of this hop built beside the next hop's sums (one launch)
-            defer = (not fork and sh and CSC_FUSE["mode"] != "off" and
+            defer = (not fork and not later and sh and CSC_FUSE["mode"] != "off" and
                      self.csc[h] is not None and self.edge_meta[h] is None and
                      h + 1 < len(self.sizes_k) and self._sums_path(h + 1, hs(h + 1), meta_only))
             L.call("regnn_ns_hop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(self.etype_csr),
@@ -252,9 +279,8 @@ class DeviceSampler:
                    *((L.ptr(self.local), L.ptr(self.edge_meta[h][0]), L.ptr(self.edge_meta[h][1]))
                      if self.edge_meta[h] is not None else (None, None, None)),
                    int(meta_only and self.meta_only[h] and self.edge_meta[h] is not None),
-                   *((L.ptr(t) for t in self.csc[h]) if self.csc[h] is not None
-                     else (None, None, None, None)),
-                   2 if fork or defer else int(sh), L.stream())
+                   *self._csc_args(h, split),
+                   4 if later else 2 if fork or defer else int(sh), L.stream())
             deferred = h if defer else -1
             if fork:
                 csc_stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -293,9 +319,7 @@ class DeviceSampler:
                *((L.ptr(self.local), L.ptr(self.edge_meta[h][0]), L.ptr(self.edge_meta[h][1]))
                  if self.edge_meta[h] is not None else (None, None, None)),
                int(meta_only and self.meta_only[h] and self.edge_meta[h] is not None),
-               *((L.ptr(t) for t in self.csc[h]) if self.csc[h] is not None
-                 else (None, None, None, None)),
-               mode, L.stream())
+               *self._csc_args(h, False), mode, L.stream())
 
     def set_seed(self, base_seed, epoch, batch_idx):
         """host-driven batches (the PyG-style iterator): seed words + a fresh dedup stamp."""
@@ -386,7 +410,8 @@ class _NsmWork(ctypes.Structure):
                 ("csc_ptr0", _P), ("csc_ent0", _P), ("csc_long0", _P),
                 ("stride", ctypes.c_int32 * _ML), ("blk_cnt", _P * _ML), ("part", ctypes.c_int32),
                 ("hub_acc", _P), ("hub_ticket", _P), ("hub_terms", _P), ("split_finalize", ctypes.c_int32),
-                ("pre_sums", ctypes.c_int32)]
+                ("pre_sums", ctypes.c_int32), ("csc_pending", ctypes.c_int32),
+                ("csc_cap_e", ctypes.c_int32), ("csc_cnt0", _P), ("csc_rank0", _P)]
 
 # include/regnn_hip.h REGNN_CSC_LONG_*: hub rows of a <= 32768-edge block, their <= 1024-entry
 # pieces, and the csc_long buffer holding ids + piece table
@@ -499,6 +524,16 @@ CSC_FORK = {"mode": os.environ.get("REGNN_NS_CSC_FORK", "off")}
 # 300 steps): 111.1-111.5 us on against 107.7-108.4 off -- the sampler's chain is not what
 # bounds the step; its waiting workgroups beside the model's kernels cost more than they save
 CSC_FUSE = {"mode": os.environ.get("REGNN_NS_CSC_FUSE", "off")}
+# "on" (default): a strided hop's transposed index in two launches with no wait between
+# workgroups (regnn_ns_hop csc_rank: counts + ranks, then every workgroup's own scan and
+# placement); "off": the single launch whose last block scans while the others spin (A/B)
+CSC_SPLIT = {"mode": os.environ.get("REGNN_NS_CSC_SPLIT", "on")}
+# "on": the fused trainer's hop 0 runs the split build's first launch only and the step's head
+# launch finishes the index on CUs it leaves idle (regnn_nsm_work csc_pending); "off" (default):
+# both launches on the sampler's queue. DESIGN section 4b has the measurements behind the default
+CSC_DEFER = {"mode": os.environ.get("REGNN_NS_CSC_DEFER", "off")}
+# the head launch's dynamic-LDS limit (re_nsm2.hip): the deferred half's LDS must fit under it
+_HEAD_LDS_MAX = 160 * 1024 - 2560
 # the fused engine's sampling lookahead G: 2G sampler slots, each step samples the batch trained
 # G steps later, and a G-step graph trains G slots while the sampler fills the other G on the
 # second queue with one fork (the graph's root) and one join (its end) -- instead of a fork and
@@ -523,10 +558,14 @@ def default_ahead(world):
     return AHEAD["steps"] if AHEAD["steps"] is not None else (16 if world == 1 else 8)
 # "on": inside a lookahead group, the sampler's outer-hop sums launch for the group's batch i
 # waits for the end of model step i - 1 (a model -> sampler edge only: the model never waits),
-# placing it beside step i's agg0 / head; N (default 2): only every N-th batch (each edge costs a
+# placing it beside step i's agg0 / head; N: only every N-th batch (each edge costs a
 # marker on the model's queue, ~4 us of idle before the next agg0; 6 x 20-step runs: on 111.0,
 # 2 110.1, 4 110.2 us; 160 steps 106.2 / 105.5 / 105.5); "off": the sampler runs free
-SUMS_ALIGN = {"mode": os.environ.get("REGNN_NS_SUMS_ALIGN", "2")}
+# "auto" (default): "on" where hop 0's transposed index is the split build (CSC_SPLIT, deferred
+# or not: the sampler's chain per batch is then 7-15 us shorter and reaches every step's edge in
+# time, so each sums launch sits beside agg0 / head), else "2" (with the single-launch index
+# "on" measured 100.2-100.6 against 99.3-99.8). DESIGN section 4b has the runs
+SUMS_ALIGN = {"mode": os.environ.get("REGNN_NS_SUMS_ALIGN", "auto")}
 # "on": the module path sizes its GEMMs' split-K for the first batch's live rows (ops.LIVE_HINT:
 # ~6 k of the 13312-row capacity at mag-10x, split 2 with a reduce); measured at hidden 512 (3 x
 # 20 steps): 578.2 against 563.0 us per step without -- the reduce costs more than the shorter
@@ -811,6 +850,29 @@ class FusedStep:
                 layout=sampler_type_layout(sampler, T), meta_unread=True)
             W.pre_sums = 1
 
+    def defer_csc(self):
+        """hop 0's transposed index finished by this step's head launch instead of the sampler's
+        queue (CSC_DEFER): the sampler's strided hop 0 then writes counts and ranks only
+        (regnn_ns_hop strided = 4) and the step runs with csc_pending. Returns whether it
+        applies: the two-layer step over strided blocks, the split build, neither CSC_FORK nor
+        CSC_FUSE, and the scan's LDS under the head launch's limit (else both launches stay on
+        the sampler's queue). No path here can raise the index's error word (index_errors)."""
+        s, W = self.sampler, self.W
+        ce = s.blocks[0].csr_idx.numel()
+        ok = (self.two_layer and s.strided and s.csc[0] is not None and
+              s.edge_meta[0] is None and
+              CSC_SPLIT["mode"] != "off" and CSC_DEFER["mode"] != "off" and
+              CSC_FORK["mode"] == "off" and CSC_FUSE["mode"] == "off" and
+              (ce + 64) * 4 <= _HEAD_LDS_MAX and
+              # the index's grid row is no wider than the head's own (ceil(cap0 / 16) blocks of
+              # 16 rows): only a fan-out of 64 exceeds it, and regnn_nsm_step refuses that
+              -(-ce // 1024) <= -(-s.caps[0] // 16))
+        s.csc_defer[0] = ok
+        W.csc_pending, W.csc_cap_e = int(ok), ce
+        if ok:
+            W.csc_cnt0, W.csc_rank0 = s.csc[0][0].data_ptr(), s.csc_rank[0].data_ptr()
+        return ok
+
     def _buf(self, addr):
         """the kept tensor whose data starts at addr."""
         return next(t for t in self.keep if torch.is_tensor(t) and t.data_ptr() == addr)
@@ -865,6 +927,14 @@ class FusedStep:
             raise RuntimeError("the sampler's latest batch did not form layer 0's input sums "
                                "(run_hops with meta_only=True and the strided layout, as the "
                                "fused step's sampling does)")
+        if self.two_layer and bool(self.W.csc_pending) != bool(self.sampler.csc_deferred[0]):
+            # told pending, but the latest batch built its index in full (the head would rebuild
+            # it from an earlier batch's ranks); or not told, and the gather would read an index
+            # nobody finished
+            raise RuntimeError("the step and the sampler's latest batch disagree about who "
+                               "finishes hop 0's transposed index (FusedStep.defer_csc: step "
+                               f"{bool(self.W.csc_pending)}, sampler "
+                               f"{bool(self.sampler.csc_deferred[0])})")
         # train / eval decides the dropout (a captured graph keeps the value it was captured with)
         self.P.p_drop = float(self.model.dropout) if self.model.training else 0.0
         with torch.cuda.device(self.device), timed("nsm_step"):
@@ -1132,6 +1202,11 @@ class NSTrainer:
         if self.adam_fused:
             for fs in (self.fused_slots if self.pipelined else [self.fused]):
                 fs.attach_adam(self.opt, self.flat)
+        # the fused engine only, where CSC_DEFER asks for it (off by default): each slot's head
+        # launch finishes the transposed index its sampler left at counts + ranks
+        if self.fused is not None:
+            for fs in (self.fused_slots if self.pipelined else [self.fused]):
+                fs.defer_csc()
         self.graphs = None
         self.exchange_in_graph = False         # capture() sets it: the all-reduce is in the graphs
         # tests: all-reduce the bucket even with one rank (the captured-exchange path on one GPU)
@@ -1287,6 +1362,12 @@ class NSTrainer:
         # record is a marker on the model's queue: ~4 us of queue idle between finalize and the
         # next agg0, measured in a kernel trace); "off": never
         mode = SUMS_ALIGN["mode"]
+        if mode == "auto":
+            s0 = self.slots[0]
+            split = (self.fused is not None and s0.strided and s0.csc[0] is not None and
+                     CSC_SPLIT["mode"] != "off" and CSC_FORK["mode"] == "off" and
+                     CSC_FUSE["mode"] == "off")
+            mode = "on" if split else "2"
         every = 0 if mode == "off" or self.fused is None else (1 if mode == "on" else int(mode))
         align = every > 0
         ends = {}
