@@ -41,7 +41,7 @@ enum { REGNN_F32 = 0, REGNN_BF16 = 1 };
  * <rows, gx_raw> / out_scale (out_scale > 0). Not combinable with edge_grad or the _next call. */
 enum { REGNN_SELF_PRESCALED = 0x100 };
 
-/* ABI version (bumped on any signature or semantics change; currently 48). */
+/* ABI version (bumped on any signature or semantics change; currently 49). */
 int regnn_abi_version(void);
 
 /* Tuning knob (process-wide, for A/B measurements; defaults are the shipped configuration).
@@ -818,7 +818,8 @@ int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t
 
 /* ---------------------------------------------------------------------------------------
  * Fused NS model step: the REGNN of mag/regnn_ns.py:216-346 (model 'regcn', self_loop_type 2,
- * use_norm 'ln', residual off, feats_type != 2, hidden 64) forward + nll_loss + backward over the
+ * use_norm 'ln', residual off or -- L = 2 -- on (regnn_nsm_params.residual), feats_type != 2,
+ * hidden 64) forward + nll_loss + backward over the
  * blocks regnn_ns_hop wrote, with no host sizes (every kernel reads the counts in `sizes`).
  * Replaces, per step (mag/regnn_ns.py:399-406): group_input's per-type Linear (:300-326), each
  * REGCNConv (x @ W, relation-table mean aggregation + bias, LayerNorm; mag/regnn_layers.py:
@@ -882,6 +883,17 @@ typedef struct regnn_nsm_params {
                                  edge capacity <= 32768, regnn_nsm_work.p0 / gh1 / csc_* set):
                                  regnn_nsm_step and regnn_nsm_slab_floats take that form only
                                  then, one decision for both; 0: the composed-map form (ABI 36) */
+    /* ABI 49. 1: every conv adds x_target @ W before its LayerNorm (the reference's residual
+     * with weight_root = weight, mag/regnn_layers.py:101-107,131-132); 0: none. Two-layer form
+     * only: LN(mean_e(ew_e x_e) W + bias + x_v W) = LN(inv_v (sum_e ew_e x_e + cnt_v x_v) W +
+     * bias) with cnt_v = 1 / inv_v the row's entries, so the row's self-loop entry (relation >=
+     * n_edge_types, which must be >= 0) takes the coefficient tab[r_self] + cnt_v in both
+     * layers' aggregations and their transposes, while the relation-table gradient still sees
+     * tab[r_self] alone. The composed-map form (two_layer == 0: L = 3 or 4, C > 384, or hop 0's
+     * edge capacity > 32768) projects before it aggregates from layer 1 on and does not cover
+     * it: with residual == 1 there, regnn_nsm_step returns REGNN_EUNSUPPORTED before any launch
+     * and regnn_nsm_slab_floats returns -REGNN_EUNSUPPORTED. Other values: REGNN_EINVAL. */
+    int32_t residual;
 } regnn_nsm_params;
 
 typedef struct regnn_nsm_work {
@@ -976,7 +988,8 @@ typedef struct regnn_nsm_adam {
 } regnn_nsm_adam;
 
 /* Floats of the per-block partial slab regnn_nsm_step needs for these parameters and a batch
- * capacity cap0 (= regnn_nsm_work.cap[0]). */
+ * capacity cap0 (= regnn_nsm_work.cap[0]); negative on parameters it rejects (-1: null / cap0 <=
+ * 0; -REGNN_EUNSUPPORTED: residual outside the two-layer form). */
 int64_t regnn_nsm_slab_floats(const regnn_nsm_params* p, int32_t cap0);
 
 /* One forward + loss + backward of the model over the current batch (after regnn_ns_batch and

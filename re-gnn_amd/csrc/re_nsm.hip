@@ -1560,6 +1560,7 @@ extern "C" {
 int64_t regnn_nsm_slab_floats(const regnn_nsm_params* p, int32_t cap0) {
     if (!p || cap0 <= 0) return -1;
     if (regnn_nsm2_covers(p)) return regnn_nsm2_slab_floats(p, cap0);
+    if (p->residual) return -int64_t(REGNN_EUNSUPPORTED);    // the two-layer form only
     return slab_layout(p, cap0).total;
 }
 
@@ -1571,6 +1572,9 @@ int regnn_nsm_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStream
         return REGNN_EUNSUPPORTED;
     for (int l = 0; l < L; ++l)
         if (p->n_rel[l] < 1 || p->n_rel[l] > F) return REGNN_EUNSUPPORTED;
+    if (p->residual != 0 && p->residual != 1) return REGNN_EINVAL;
+    // the composed-map form projects before it aggregates from layer 1 on: no residual there
+    if (p->residual && !regnn_nsm2_covers(p)) return REGNN_EUNSUPPORTED;
     if (!w->state || !w->sizes || !w->n_id || !w->ntype || !w->local || !w->labels || !w->wc ||
         !w->gwc || !w->tabs || !w->nvalid || !w->edge_type || !w->edge_off || !w->s_agg ||
         !w->s_w || !w->z || !w->beta || !w->slab ||
@@ -1595,6 +1599,8 @@ int regnn_nsm_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStream
     if (rs && (!w->u_self || !w->u_rel || p->n_edge_types < 0 || p->n_edge_types + T > p->n_rel[0]))
         return REGNN_EINVAL;
     if (w->part < 0 || w->part > 2) return REGNN_EINVAL;
+    // residual: the self loops are told apart by relation >= n_edge_types in either mode
+    if (p->residual && p->n_edge_types < 0) return REGNN_EINVAL;
     if (regnn_nsm2_covers(p)) return regnn_nsm2_step(p, w, stream);
     // the fused optimizer, the strided blocks and the split into parts: two-layer step only
     if (w->part) return REGNN_EUNSUPPORTED;

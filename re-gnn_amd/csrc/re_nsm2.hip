@@ -25,6 +25,14 @@
 //   rel0      (no relation slots) layer 0's relation-table dots edge by edge (re_nsm.hip).
 //   finalize  every gradient as a fixed-order sum of per-block partials; with an optimizer
 //             attached, Adam (regnn_adam_flat's arithmetic) on each element right after its sum.
+//
+// Residual convs (regnn_nsm_params.residual; mag/regnn_layers.py:101-107,131-132 with weight_root
+// = weight): LN(mean_e(ew_e x_e) W + bias + x_v W) = LN(inv_v (sum_e ew_e x_e + cnt_v x_v) W + bias),
+// cnt_v = 1 / inv_v the row's entries, and row v's own row is already its self-loop entry
+// (relation >= n_edge_types): that entry's coefficient becomes tab[r_self] + cnt_v in agg0, head,
+// the gather's row sums and bwd0's re-formed S, while the relation-table gradients keep
+// tab[r_self]'s own term. The residual forms of agg0w / head / gather / bwd0 are template
+// instantiations (RES), so the non-residual kernels keep their instruction streams.
 #include "re_nsm_common.h"
 #include "re_csc_place.h"
 
@@ -136,6 +144,11 @@ struct Agg0Args {
     // relation slots (RS): s_agg / s_w hold the unweighted sums / counts of the non-self edges
     // per source type, u_self the self loop's input row, u_rel [n][T + 1] each slot's relation
     int n_et; float* u_self; int32_t* u_rel;
+    // residual (regnn_nsm_params.residual): the conv adds x_target W, i.e. the row's self-loop
+    // entry takes tab[r_self] + cnt_v (cnt_v = the row's entries, 1 / inv_v) in place of
+    // tab[r_self]. agg0_kernel reads it (wave-uniform; 0 skips the terms), agg0w_kernel is
+    // instantiated for it (RES)
+    int residual;
 };
 
 // LDS: S tile [16][T K + 4] | s_w [16][MT] | P [16][68] | pre-LN rows [16][64] | table [64] |
@@ -233,6 +246,8 @@ __global__ void __launch_bounds__(kBlock, 2) agg0_kernel(Agg0Args A) {
                     my_lo = int(A.edge_off[c0 + l]);
                     my_r = A.rel[c0 + l];
                     my_w = tab[my_r];
+                    if constexpr (!RS)             // residual: the self loop's coefficient
+                        if (A.residual && my_r >= A.n_et) my_w += float(e1 - e0);
                 }
                 constexpr int UN = 8;              // edges' rows in flight per lane
                 for (int j = 0; j < m; j += UN) {
@@ -293,6 +308,14 @@ __global__ void __launch_bounds__(kBlock, 2) agg0_kernel(Agg0Args A) {
         PH(0, 1);
         if constexpr (PD == 1) bload(0, bq[0]);      // (8 node types: after the gather)
         const int tau = r_self - A.n_et;           // RS: the row's node type
+        float cres = 0.f;                          // RS, residual: cnt_v = the slots' counts + 1
+        if constexpr (RS) {
+            if (A.residual) {
+                cres = 1.f;
+#pragma unroll
+                for (int tt = 0; tt < NT; ++tt) cres += wsum[tt];
+            }
+        }
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) {
             if (tt < T) {
@@ -300,6 +323,7 @@ __global__ void __launch_bounds__(kBlock, 2) agg0_kernel(Agg0Args A) {
                 if constexpr (RS) {
                     wr = rel_t[tt] >= 0 ? tab[rel_t[tt]] : 0.f;
                     ws = (tt == tau) ? tab[r_self] : 0.f;
+                    if (A.residual) ws = (tt == tau) ? tab[r_self] + cres : 0.f;
                 }
 #pragma unroll
                 for (int p = 0; p < VPL; ++p) {
@@ -437,7 +461,9 @@ inline size_t agg0w_lds(int T) {          // St [16][T K + 4] | sw [16][MT] | Pt
 // PRE (relation slots): the row's per-type input sums, counts, self row and slot relations were
 // formed by the sampler (regnn_ns_hop_typed_sums into s_agg / s_w / u_self / u_rel): the gather
 // phase is one round of contiguous loads, and nothing of them is written here
-template <int NT, bool RS, bool PRE = false>
+// RES: the residual form (Agg0Args.residual set), an instantiation of its own so that the
+// benchmarked non-residual kernels keep their instruction streams
+template <int NT, bool RS, bool PRE = false, bool RES = false>
 __global__ void __launch_bounds__(kAggW, 4) agg0w_kernel(Agg0Args A) {
     static_assert(!PRE || RS, "the sampler's sums need relation slots");
     constexpr int K = 128, HB = K / 32;    // float4 steps per half type (stage 1)
@@ -537,6 +563,9 @@ __global__ void __launch_bounds__(kAggW, 4) agg0w_kernel(Agg0Args A) {
         if constexpr (!RS) {
             const float tr = A.rw[min(my_r, A.n_rel - 1)] * A.alpha;
             my_w = my_r < A.n_rel ? (tr > 0.f ? tr : 0.01f * tr) : 0.f;
+            // residual: the self loop's coefficient
+            if constexpr (RES)
+                if (my_r >= A.n_et) my_w += float(e1 - e0);
         }
         for (int j = 0; j < m; j += UN) {
             int t[UN], ru[UN];
@@ -583,6 +612,12 @@ __global__ void __launch_bounds__(kAggW, 4) agg0w_kernel(Agg0Args A) {
     }
     PH(0, 1);
     const int tau = r_self - A.n_et;           // RS: the row's node type
+    float cres = 0.f;                          // RS, residual: cnt_v = the slots' counts + 1
+    if constexpr (RS && RES) {
+        cres = 1.f;
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) cres += wsum[tt];
+    }
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) {
         if (tt < T) {
@@ -592,6 +627,7 @@ __global__ void __launch_bounds__(kAggW, 4) agg0w_kernel(Agg0Args A) {
                 const float tsf = __shfl(tabw, max(r_self, 0), 64);
                 wr = rel_t[tt] >= 0 ? tr : 0.f;
                 ws = (tt == tau) ? tsf : 0.f;
+                if constexpr (RES) ws = (tt == tau) ? tsf + cres : 0.f;
             }
             float4 sv = racc[tt];
             if constexpr (RS)
@@ -760,6 +796,9 @@ struct HeadArgs {
     const float* w_out; const float* b_out; int C;
     float* gh; float* nvalid; float* part; int64_t part_w;
     float* g_rows; float* h_rows;          // [blocks * 16][C] softmax gradient, [blocks * 16][64] h
+    // residual (head_kernel<true>): Hagg[v] += cnt_v h0[v] as the self-loop entry's coefficient
+    // tab[r_self] + cnt_v (entries with a relation >= n_et are the self loops)
+    int n_et;
     // the grid's second row (blockIdx.y = 1, launched only with regnn_nsm_work csc_pending)
     // finishes hop 0's transposed index (csc_scan_place, re_csc_place.h) on CUs the head leaves
     // idle; the gather reads it next. The row is told apart by a register, not by a kernel
@@ -793,6 +832,9 @@ constexpr int kHeadSL = kHeadThreads / 16; // softmax lanes per row
 constexpr int kHeadNQ = kHeadW / 4;        // gh: class parts (4 feature tiles x kHeadNQ)
 static_assert(kHeadNQ == 4 && kHeadSL == 64, "step 4c / 4d sum four class parts; 4b a wave per row");
 
+// RES: the residual form, an instantiation of its own (as a kernel argument the flag cost the
+// non-residual step ~0.3 us in this kernel: its selects sit on the aggregation's chain)
+template <bool RES>
 __global__ void __launch_bounds__(kHeadThreads, 1) head_kernel(HeadArgs A) {
     extern __shared__ float hl[];
     if (__builtin_expect(blockIdx.y != 0, 0)) {    // block-uniform, ahead of every barrier
@@ -843,6 +885,8 @@ __global__ void __launch_bounds__(kHeadThreads, 1) head_kernel(HeadArgs A) {
                 const int my_r0 = l < m ? int(A.rel[c0 + l]) : 0;
                 const int my_u1 = l + 16 < m ? A.idx[c0 + 16 + l] : 0;
                 const int my_r1 = l + 16 < m ? int(A.rel[c0 + 16 + l]) : 0;
+                // residual: this lane's entries that are the row's self loop
+                const bool sf0 = RES && my_r0 >= A.n_et, sf1 = RES && my_r1 >= A.n_et;
                 constexpr int UN = 32;
                 float4 x[UN];
 #pragma unroll
@@ -855,8 +899,12 @@ __global__ void __launch_bounds__(kHeadThreads, 1) head_kernel(HeadArgs A) {
                 // rows are requested), broadcast by shuffles
                 const float tr0 = A.rw[min(my_r0, A.n_rel - 1)] * A.alpha;
                 const float tr1 = A.rw[min(my_r1, A.n_rel - 1)] * A.alpha;
-                const float w0 = my_r0 < A.n_rel ? (tr0 > 0.f ? tr0 : 0.01f * tr0) : 0.f;
-                const float w1 = my_r1 < A.n_rel ? (tr1 > 0.f ? tr1 : 0.01f * tr1) : 0.f;
+                const float t0 = my_r0 < A.n_rel ? (tr0 > 0.f ? tr0 : 0.01f * tr0) : 0.f;
+                const float t1 = my_r1 < A.n_rel ? (tr1 > 0.f ? tr1 : 0.01f * tr1) : 0.f;
+                // (selects, not branches: a branch here keeps all 32 rows live across it;
+                // lanes past m hold weights nobody reads)
+                const float cr = RES ? float(e1 - e0) : 0.f;
+                const float w0 = sf0 ? t0 + cr : t0, w1 = sf1 ? t1 + cr : t1;
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {     // branch-free: a padding entry (a clamped
                     // valid row) gets weight 0, which adds exact zeros
@@ -1147,6 +1195,11 @@ struct GathArgs {
     // backward and adds its row terms to hub_terms [3][64] (all exact 2^-40 integers; hub_acc /
     // hub_ticket zeroed by that group, hub_terms by finalize); hub_terms[192]: the overflow flag
     unsigned long long* hub_acc; int32_t* hub_ticket; unsigned long long* hub_terms;
+    // residual (gather_kernel<true>): a batch target u's self entry (relation >= n_et; each row
+    // has one, in exactly one piece of a hub row) takes tab[r_self] + cnt_u in the row sums,
+    // cnt_u = 1 / inv0[u] u's entries in hop 0's block (inv0: the head's row scales, 1 / an
+    // integer); the relation dots do not
+    const float* inv0; int n_et;
 };
 
 // 512 threads (32 row groups) per block: a hub piece's entries over 32 groups (a 439-entry row:
@@ -1162,6 +1215,12 @@ constexpr int kShort = 16;                 // = re_ns.hip kCscShort
 struct RowIn {                             // one lane's 4 features of layer 0's row u
     float xh[4], yv[4], mk[4], h0[4], rstd, iv;
 };
+
+// residual: cnt_u of layer-0 row u (0 for the rows that are no batch target: they have no self
+// entry in hop 0's transposed index, so nothing reads it)
+__device__ __forceinline__ float row_cres(const GathArgs& A, int u) {
+    return u < A.sizes[0] ? rintf(1.f / A.inv0[u]) : 0.f;
+}
 
 __device__ __forceinline__ RowIn row_in(const GathArgs& A, uint32_t key, int u, int l,
                                          const float (&lw)[4], const float (&lb)[4]) {
@@ -1184,11 +1243,12 @@ __device__ __forceinline__ RowIn row_in(const GathArgs& A, uint32_t key, int u, 
 // `m` entries of a segment starting at c (m <= 16, uniform over the group): fixed-point sums of
 // tab[r] GH[v] into acc and the relation dots into the block's bins
 // `my`: lane l's entry word of the chunk (l < m), loaded by the caller
-template <int UN>
+template <int UN, bool RES>
 __device__ __forceinline__ void gather_chunk_my(const GathArgs& A, const float* tab,
                                                 unsigned long long (&rb)[4], int my, int m, int l,
                                                 int gl, const RowIn& R,
-                                                unsigned long long (&acc)[4], bool& bad) {
+                                                unsigned long long (&acc)[4], bool& bad,
+                                                float cres) {
     for (int j = 0; j < m; j += UN) {
         int pk[UN];
         float4 g[UN];
@@ -1203,7 +1263,9 @@ __device__ __forceinline__ void gather_chunk_my(const GathArgs& A, const float* 
                                                // unrolls, a break leaves g[] in scratch; a
                                                // branch-free form computed the short rows'
                                                // padding too: the gather 4.0 -> 6.2 us p50)
-            const float t = tab[pk[u] & 255];
+            float t = tab[pk[u] & 255];
+            if constexpr (RES)
+                if ((pk[u] & 255) >= A.n_et) t += cres;    // the row's self entry
             acc[0] += to_fix_chk(t * g[u].x, bad);
             acc[1] += to_fix_chk(t * g[u].y, bad);
             acc[2] += to_fix_chk(t * g[u].z, bad);
@@ -1223,13 +1285,14 @@ __device__ __forceinline__ void gather_chunk_my(const GathArgs& A, const float* 
     }
 }
 
-template <int UN>
+template <int UN, bool RES>
 __device__ __forceinline__ void gather_chunk(const GathArgs& A, const float* tab,
                                              unsigned long long (&rb)[4], int c, int m, int l,
                                              int gl, const RowIn& R,
-                                             unsigned long long (&acc)[4], bool& bad) {
+                                             unsigned long long (&acc)[4], bool& bad,
+                                             float cres) {
     const int my = l < m ? A.cent[c + l] : 0;
-    gather_chunk_my<UN>(A, tab, rb, my, m, l, gl, R, acc, bad);
+    gather_chunk_my<UN, RES>(A, tab, rb, my, m, l, gl, R, acc, bad, cres);
 }
 
 // the LayerNorm / relu / dropout backward of row u from its sums; G0 row to HBM, row terms
@@ -1279,6 +1342,9 @@ __device__ __forceinline__ void hub_row_bwd(const GathArgs& A, int u, int l, con
 // in LDS. A row of one piece finishes there; a longer row's pieces store their sums to
 // hub_acc[j] and the piece that completes the row's ticket sums them (exact) and runs the row's
 // backward (device-scope fences: only for rows past 1024 entries).
+// RES: the residual form, an instantiation of its own (as a kernel argument the flag cost the
+// non-residual step ~0.4 us here: a compare and a select per entry, two spilled SGPRs)
+template <bool RES>
 __global__ void __launch_bounds__(kGathT) gather_kernel(GathArgs A) {
     __shared__ unsigned long long bins[F];
     __shared__ unsigned long long lgh[F];
@@ -1311,14 +1377,15 @@ __global__ void __launch_bounds__(kGathT) gather_kernel(GathArgs A) {
         const int li = pc.w >> 16, k = (pc.w >> 8) & 255, npc = pc.w & 255;
         PG(j, 0);
         const RowIn R = row_in(A, key, u, l, lw, lb);
+        const float cres = RES ? row_cres(A, u) : 0.f;
         unsigned long long acc[4] = {0ull, 0ull, 0ull, 0ull};
         // the piece's entries in even shares over the 32 groups (a 64-entry row: 2 per group,
         // not 16 on each of four); chunk width by the share (block-uniform)
         const int per = (cnt + kGathG - 1) / kGathG, g0 = min(cnt, per * grp), g1 = min(cnt, g0 + per);
         if (per <= 4) {
-            if (g1 > g0) gather_chunk<4>(A, tab, rb, e0 + g0, g1 - g0, l, gl, R, acc, bad);
+            if (g1 > g0) gather_chunk<4, RES>(A, tab, rb, e0 + g0, g1 - g0, l, gl, R, acc, bad, cres);
         } else if (per <= 8) {
-            if (g1 > g0) gather_chunk<8>(A, tab, rb, e0 + g0, g1 - g0, l, gl, R, acc, bad);
+            if (g1 > g0) gather_chunk<8, RES>(A, tab, rb, e0 + g0, g1 - g0, l, gl, R, acc, bad, cres);
         } else {                               // <= 64 entries: up to 4 chunks, whose entry
             int myk[4];                        // words are all requested first
 #pragma unroll
@@ -1329,7 +1396,7 @@ __global__ void __launch_bounds__(kGathT) gather_kernel(GathArgs A) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int ck = g0 + kShort * k, mk = min(kShort, g1 - ck);
-                if (mk > 0) gather_chunk_my<kShort>(A, tab, rb, myk[k], mk, l, gl, R, acc, bad);
+                if (mk > 0) gather_chunk_my<kShort, RES>(A, tab, rb, myk[k], mk, l, gl, R, acc, bad, cres);
             }
         }
         PG(j, 1);
@@ -1385,8 +1452,9 @@ __global__ void __launch_bounds__(kGathT) gather_kernel(GathArgs A) {
         const int c0 = A.cptr[u], m = A.cptr[u + 1] - c0;
         if (m > kShort) continue;              // a hub: its pieces above
         const RowIn R = row_in(A, key, u, l, lw, lb);
+        const float cres = RES ? row_cres(A, u) : 0.f;
         unsigned long long acc[4] = {0ull, 0ull, 0ull, 0ull};
-        gather_chunk<8>(A, tab, rb, c0, m, l, gl, R, acc, bad);
+        gather_chunk<8, RES>(A, tab, rb, c0, m, l, gl, R, acc, bad, cres);
         row_bwd(A, u, l, R, lw, acc, sga, sgy, sgyx);
     }
 #pragma unroll
@@ -1453,8 +1521,13 @@ constexpr size_t bwd0_lds_floats(int n_rel) {
 // groups' W_t image is shared and their partials meet in LDS (group 0 + group 1, fixed order)
 // before one slab row per block: NG = 2 with half the blocks keeps the waves per CU and halves
 // the split-K slab finalize reads.
-template <int K, bool RS, int NG>
+// RES (residual with relation slots; an instantiation of its own, as agg0w's): the re-formed
+// S = wr U + ws x_self takes agg0's ws = tab[r_self] + cnt_v (cnt_v = the row's slot counts + 1);
+// the relation bins keep tab[r_self]'s own gradient. The edge pass reads s_agg / s_w, which carry
+// the residual part already
+template <int K, bool RS, int NG, bool RES = false>
 __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
+    static_assert(!RES || RS, "the edge pass's sums carry the residual part");
     static_assert(NG == 1 || NG == 2, "one or two wave groups");
     constexpr int XS = K + 4, GS = F + 16, G2 = F + 4, WS = F + 4;
     constexpr int KB = K / 64;                // k blocks per wave
@@ -1520,7 +1593,7 @@ __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
     // prefetched rows of the next tile
     float4 ur[XV], xr[XV];
     float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f), p4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float cntv = 0.f;
+    float cntv = 0.f, cresv = 0.f;
     int relv = -1, rsv = -1;
     auto load = [&](int v0) {
 #pragma unroll
@@ -1548,6 +1621,10 @@ __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
             if constexpr (RS) {
                 relv = ok ? A.u_rel[int64_t(vv) * (T + 1) + t] : -1;
                 rsv = ok ? A.u_rel[int64_t(vv) * (T + 1) + T] : -1;
+                if constexpr (RES) {           // cnt_v, as agg0 formed it (exact small integers)
+                    cresv = 1.f;
+                    for (int tt = 0; tt < T; ++tt) cresv += ok ? A.s_w[int64_t(vv) * T + tt] : 0.f;
+                }
             }
         }
     };
@@ -1569,6 +1646,7 @@ __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
                     const bool self = rsv >= 0 && rsv - A.n_et == t;
                     rm[4 * tid] = relv >= 0 ? tabl[relv] : 0.f;
                     rm[4 * tid + 1] = self ? tabl[rsv] : 0.f;
+                    if constexpr (RES) rm[4 * tid + 1] = self ? tabl[rsv] + cresv : 0.f;
                     rr[2 * tid] = (relv >= 0 && cntv > 0.f) ? relv : -1;
                     rr[2 * tid + 1] = self ? rsv : -1;
                 } else {
@@ -2222,20 +2300,24 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         A.a = w->a[0]; A.stats = w->stats[0]; A.h = w->xs[1]; A.p = w->p0;
         A.n_et = p->n_edge_types; A.u_self = w->u_self; A.u_rel = w->u_rel;
         A.n_id = w->n_id; A.labels = w->labels; A.nvalid = w->nvalid;
+        A.residual = p->residual;
         int grid = (w->cap[h] + 15) / 16;
         if (pre && (K != 128 || T > 4 || !rs)) return REGNN_EINVAL;
         if (K == 128 && T <= 4 && (pre || !getenv("REGNN_NSM_AGG0_OLD"))) {  // every tile its own block
             grid = (w->cap[h] + kAggRows - 1) / kAggRows;
             const size_t lds = agg0w_lds(T);
-#define AGG0W_CASE(NN, RS, PRE)                                                                \
-            if (rs == RS && pre == PRE) {                                                      \
+            const bool res = p->residual != 0;
+#define AGG0W_CASE(NN, RS, PRE, RES)                                                           \
+            if (rs == RS && pre == PRE && res == RES) {                                        \
                 static size_t done = 0;                                                        \
-                if (!set_lds(reinterpret_cast<const void*>(&agg0w_kernel<NN, RS, PRE>), lds, &done)) \
+                if (!set_lds(reinterpret_cast<const void*>(&agg0w_kernel<NN, RS, PRE, RES>), lds, &done)) \
                     return REGNN_EUNSUPPORTED;                                                 \
-                hipLaunchKernelGGL((agg0w_kernel<NN, RS, PRE>), dim3(grid), dim3(kAggW), lds, stream, A); \
+                hipLaunchKernelGGL((agg0w_kernel<NN, RS, PRE, RES>), dim3(grid), dim3(kAggW), lds, stream, A); \
                 REGNN_LAUNCH_CHECK();                                                          \
             } else
-            AGG0W_CASE(4, true, true) AGG0W_CASE(4, true, false) AGG0W_CASE(4, false, false)
+            AGG0W_CASE(4, true, true, false) AGG0W_CASE(4, true, false, false)
+            AGG0W_CASE(4, false, false, false) AGG0W_CASE(4, true, true, true)
+            AGG0W_CASE(4, true, false, true) AGG0W_CASE(4, false, false, true)
                 return REGNN_EUNSUPPORTED;
 #undef AGG0W_CASE
         } else {
@@ -2269,6 +2351,7 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         H.w_out = p->out_w; H.b_out = p->out_b; H.C = C;
         H.gh = w->gh1; H.nvalid = w->nvalid; H.part = w->slab + S.head; H.part_w = hw;
         H.g_rows = w->slab + S.hg; H.h_rows = w->slab + S.hh;
+        H.n_et = p->n_edge_types;
         size_t lds = head_lds(C);
         int extra = 0;
         if (w->csc_pending) {
@@ -2282,15 +2365,19 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
             extra = csc_place_blocks(ce);
             if (csc_place_lds(ce) > lds) lds = csc_place_lds(ce);
         }
-        static size_t done = 0;
-        if (!set_lds(reinterpret_cast<const void*>(&head_kernel), lds, &done))
-            return REGNN_EUNSUPPORTED;
+        static size_t done[2] = {0, 0};
+        const void* hk = p->residual ? reinterpret_cast<const void*>(&head_kernel<true>)
+                                     : reinterpret_cast<const void*>(&head_kernel<false>);
+        if (!set_lds(hk, lds, &done[p->residual ? 1 : 0])) return REGNN_EUNSUPPORTED;
         // pending: a second grid row for the index (its blocks past `extra` leave at once). The
         // row is never wider than the head's: extra <= head_blocks was checked above, so row 0
         // holds exactly the head's workgroups, whose slab rows slab2() sized
         static_assert(kHeadThreads == kCscPlaceT, "csc_scan_place runs on 1024 threads");
         const dim3 grid(S.head_blocks, extra ? 2 : 1);
-        hipLaunchKernelGGL(head_kernel, grid, dim3(kHeadThreads), lds, stream, H);
+        if (p->residual)
+            hipLaunchKernelGGL(head_kernel<true>, grid, dim3(kHeadThreads), lds, stream, H);
+        else
+            hipLaunchKernelGGL(head_kernel<false>, grid, dim3(kHeadThreads), lds, stream, H);
         REGNN_LAUNCH_CHECK();
     }
     // 3. layer 1's transposed aggregation (a gather), layer 0's LayerNorm backward
@@ -2303,7 +2390,11 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         G.rw = p->conv_rw[1]; G.n_rel = p->n_rel[1]; G.alpha = p->alpha;
         G.g0 = w->ga[0]; G.slab = w->slab + S.gath;
         G.hub_acc = w->hub_acc; G.hub_ticket = w->hub_ticket; G.hub_terms = w->hub_terms;
-        hipLaunchKernelGGL(gather_kernel, dim3(kGathBlocks), dim3(kGathT), 0, stream, G);
+        G.inv0 = w->blk_inv[0]; G.n_et = p->n_edge_types;
+        if (p->residual)
+            hipLaunchKernelGGL(gather_kernel<true>, dim3(kGathBlocks), dim3(kGathT), 0, stream, G);
+        else
+            hipLaunchKernelGGL(gather_kernel<false>, dim3(kGathBlocks), dim3(kGathT), 0, stream, G);
         REGNN_LAUNCH_CHECK();
         if (split) {
             JobList J;
@@ -2325,17 +2416,21 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         B.slab = w->slab + S.proj; B.rslab = w->slab + S.rel0; B.slab0 = w->slab + S.post0;
         B.adam_step = ad ? ad->step : nullptr;
         const dim3 grid(nb0, T);
-#define BWD0_CASE(KK, RS, NG)                                                                  \
-        if (K == KK && rs == RS && kBwdGroups == NG) {                                         \
+        const bool res = rs && p->residual != 0;
+#define BWD0_CASE(KK, RS, NG, RES)                                                             \
+        if (K == KK && rs == RS && kBwdGroups == NG && res == RES) {                           \
             static size_t done = 0;                                                            \
             const size_t lds = bwd0_lds_floats<KK, RS, NG>(p->n_rel[0]) * sizeof(float);       \
-            if (!set_lds(reinterpret_cast<const void*>(&bwd0_kernel<KK, RS, NG>), lds, &done)) \
+            if (!set_lds(reinterpret_cast<const void*>(&bwd0_kernel<KK, RS, NG, RES>), lds, &done)) \
                 return REGNN_EUNSUPPORTED;                                                     \
-            hipLaunchKernelGGL((bwd0_kernel<KK, RS, NG>), grid, dim3(kBlock * NG), lds, stream, B); \
+            hipLaunchKernelGGL((bwd0_kernel<KK, RS, NG, RES>), grid, dim3(kBlock * NG), lds, stream, B); \
             REGNN_LAUNCH_CHECK();                                                              \
         } else
-        BWD0_CASE(128, true, 2) BWD0_CASE(64, true, 2) BWD0_CASE(128, false, 2) BWD0_CASE(64, false, 2)
-        BWD0_CASE(128, true, 1) BWD0_CASE(64, true, 1) BWD0_CASE(128, false, 1) BWD0_CASE(64, false, 1)
+        BWD0_CASE(128, true, 2, false) BWD0_CASE(64, true, 2, false) BWD0_CASE(128, false, 2, false)
+        BWD0_CASE(64, false, 2, false) BWD0_CASE(128, true, 1, false) BWD0_CASE(64, true, 1, false)
+        BWD0_CASE(128, false, 1, false) BWD0_CASE(64, false, 1, false)
+        BWD0_CASE(128, true, 2, true) BWD0_CASE(64, true, 2, true)
+        BWD0_CASE(128, true, 1, true) BWD0_CASE(64, true, 1, true)
             return REGNN_EUNSUPPORTED;
 #undef BWD0_CASE
     }

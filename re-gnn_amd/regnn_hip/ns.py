@@ -395,7 +395,7 @@ class _NsmParams(ctypes.Structure):
                 ("g_conv_b", _P * _ML), ("g_conv_rw", _P * _ML), ("g_ln_w", _P * _ML),
                 ("g_ln_b", _P * _ML), ("g_out_w", _P), ("g_out_b", _P), ("loss", _P),
                 ("n_edge_types", ctypes.c_int32), ("rel_slots", ctypes.c_int32),
-                ("two_layer", ctypes.c_int32)]
+                ("two_layer", ctypes.c_int32), ("residual", ctypes.c_int32)]
 
 
 class _NsmWork(ctypes.Structure):
@@ -440,13 +440,19 @@ class _NsmAdam(ctypes.Structure):
 
 # regnn_nsm_step's two-layer form (re_nsm2.hip): L = 2 and at most 384 classes (its head's LDS)
 TWO_LAYER_MAX_CLASSES = 384
+# ... and a hop-0 block of at most this many entries (its transposed index)
+TWO_LAYER_MAX_EDGES = 32768
+_RESIDUAL_TWO_LAYER = ("residual convs run in the fused step's two-layer form only "
+                       f"(2 layers, <= {TWO_LAYER_MAX_CLASSES} classes, hop-0 block capacity "
+                       f"<= {TWO_LAYER_MAX_EDGES})")
 
 
 def fused_unsupported(model, x_dict):
     """why regnn_nsm_step cannot run this model (None: it can). The fused step covers the
     reference configuration of mag/regnn_ns.py: model 'regcn', self_loop_type 2, use_norm 'ln',
-    no residual, feats_type != 2, hidden 64, equal input widths 64 / 128, <= 8 node types,
-    2..4 layers, <= 448 classes."""
+    feats_type != 2, hidden 64, equal input widths 64 / 128, <= 8 node types, 2..4 layers,
+    <= 448 classes; residual on every conv or on none, and residual in the two-layer form only
+    (2 layers, <= TWO_LAYER_MAX_CLASSES classes; FusedStep also checks the hop-0 capacity)."""
     if getattr(model, "model", None) != "regcn" or getattr(model, "feats_type", 3) == 2:
         return "model is not the feats_type-3 regcn"
     if model.self_loop_type != 2:
@@ -454,9 +460,12 @@ def fused_unsupported(model, x_dict):
     convs = list(model.convs)
     if not 2 <= len(convs) <= _ML:
         return "2..4 layers"
+    res = [bool(c.residual) for c in convs]
+    if any(res) and not all(res):
+        return "mixed residual flags across the convs"
     for c in convs:
-        if c.residual or c.use_norm != "ln" or tuple(c.weight.shape) != (64, 64):
-            return "conv needs LayerNorm, no residual, hidden 64"
+        if c.use_norm != "ln" or tuple(c.weight.shape) != (64, 64):
+            return "conv needs LayerNorm, hidden 64"
         if c.relation_weight.numel() > 64 or abs(c.scaling_factor - convs[0].scaling_factor) > 0:
             return "relation table > 64 or mixed scaling factors"
     keys = sorted(x_dict)
@@ -472,6 +481,19 @@ def fused_unsupported(model, x_dict):
         return "inputs must be contiguous fp32"
     if model.out_lin.weight.shape[0] > 448 or model.out_lin.weight.shape[1] != 64:
         return "out_lin must be 64 -> <= 448"
+    if res[0] and (len(convs) != 2 or model.out_lin.weight.shape[0] > TWO_LAYER_MAX_CLASSES):
+        return _RESIDUAL_TWO_LAYER
+    return None
+
+
+def fused_residual_unsupported(model, sampler):
+    """why regnn_nsm_step cannot run this residual model over this sampler's blocks (None: it
+    can, or the model has no residual convs): a hop-0 block past the two-layer form's transposed
+    index would take the composed-map form, which has no residual."""
+    if not any(bool(c.residual) for c in model.convs):
+        return None
+    if sampler.blocks[0].csr_idx.numel() > TWO_LAYER_MAX_EDGES:
+        return _RESIDUAL_TWO_LAYER
     return None
 
 
@@ -731,10 +753,16 @@ def sampler_type_layout(sampler, T):
 class FusedStep:
     """regnn_nsm_step over a DeviceSampler's blocks: the model's forward, nll loss and backward
     in eight launches (two layers), gradients written straight into each parameter's .grad (the
-    caller's flat bucket views), loss into `loss`. Keeps every buffer it points the library at."""
+    caller's flat bucket views), loss into `loss`. Keeps every buffer it points the library at.
+    A model with residual convs runs in the two-layer form only (P.residual); where that form
+    does not apply (fused_residual_unsupported) the constructor raises ValueError."""
 
     def __init__(self, model, sampler, x_dict, node_type, local_node_idx, y_flat, loss):
         why = fused_unsupported(model, x_dict)
+        if why is not None:
+            raise ValueError(f"regnn_nsm_step does not cover this model: {why}")
+        # (before anything of the sampler is changed and before any launch)
+        why = fused_residual_unsupported(model, sampler)
         if why is not None:
             raise ValueError(f"regnn_nsm_step does not cover this model: {why}")
         dev = sampler.device
@@ -808,10 +836,11 @@ class FusedStep:
         W.nvalid = ptr(z(1))
         # the two-layer step: layer 0 rows' fixed-point gradient sums and group_input's projection
         self.two_layer = (nl == 2 and C <= TWO_LAYER_MAX_CLASSES and
-                          sampler.blocks[0].csr_idx.numel() <= 32768)
+                          sampler.blocks[0].csr_idx.numel() <= TWO_LAYER_MAX_EDGES)
         # one decision for the library's slab size and step (regnn_nsm_params.two_layer): a
         # batch whose hop-0 block exceeds the transposed index runs the composed-map form
         P.two_layer = int(self.two_layer)
+        P.residual = int(bool(model.convs[0].residual))
         if self.two_layer:
             W.p0 = ptr(z(caps[1], 64))
             W.gh1 = ptr(z(caps[0], 64))
@@ -1110,6 +1139,10 @@ class NSTrainer:
         # Two-layer fused step: the gradients final after layer 1's transposed pass lead the
         # bucket ([0, n_early)), so several ranks all-reduce them while layer 0's backward runs.
         why = fused_unsupported(model, x_dict)
+        if why is None:
+            # a residual model whose hop-0 block exceeds the two-layer form: "auto" takes the
+            # module path for every slot, "fused" gets FusedStep's error (below)
+            why = fused_residual_unsupported(model, self.slots[0])
         early = []
         if engine != "module" and why is None and len(model.convs) == 2:
             ids = {id(p) for p in self.params}
