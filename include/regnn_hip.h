@@ -41,7 +41,7 @@ enum { REGNN_F32 = 0, REGNN_BF16 = 1 };
  * <rows, gx_raw> / out_scale (out_scale > 0). Not combinable with edge_grad or the _next call. */
 enum { REGNN_SELF_PRESCALED = 0x100 };
 
-/* ABI version (bumped on any signature or semantics change; currently 49). */
+/* ABI version (bumped on any signature or semantics change; currently 50). */
 int regnn_abi_version(void);
 
 /* Tuning knob (process-wide, for A/B measurements; defaults are the shipped configuration).
@@ -651,7 +651,10 @@ int regnn_ns_batch(const int64_t* perm, int64_t n_perm, int32_t batch, int32_t r
  * prefix[source] + rank, workgroup 0 also writing csc_ptr, the hub list and the piece table (the
  * same values and layout; the error word is never raised). strided = 4 (needs csc_rank): the
  * first of the two only -- csc_cnt / csc_rank / blk_idx final, csc_ptr / csc_ent / csc_long
- * not written; regnn_nsm_step with csc_pending = 1 finishes the index beside its head. */
+ * not written; regnn_nsm_step with csc_pending = 1 finishes the index beside its head.
+ * strided = 5 (ABI 50; needs csc_rank, the transposed index, no edge meta): the second of the two
+ * only (scan + placement, one launch) -- for a hop whose call ran with strided = 2 and whose
+ * counts and ranks a later regnn_ns_hop_typed_sums launch wrote (regnn_ns_csc_job kind 1). */
 #define REGNN_CSC_PIECE 1024
 #define REGNN_CSC_LONG_CAP (32768 / 17 + 1)          /* hub rows of a <= 32768-edge block */
 #define REGNN_CSC_LONG_NPIECE (REGNN_CSC_LONG_CAP + 1)
@@ -683,7 +686,14 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
  * One launch. The summation order is fixed (the result is a function of the batch).
  * csc (may be NULL; ABI 42): an earlier hop's transposed index, whose regnn_ns_hop call ran with
  * strided = 2 (de-duplication done, index left out), built by extra workgroups of the same launch
- * (regnn_ns_hop strided = 3's work, beside the sums instead of before them; same state / sizes). */
+ * (regnn_ns_hop strided = 3's work, beside the sums instead of before them; same state / sizes).
+ * kind (ABI 50) REGNN_NS_CSC_JOB_RANK: the leading ceil(cap_e / 256) workgroups write only the
+ * split build's first half (regnn_ns_hop strided = 4's counts, ranks and local source ids: no
+ * wait between workgroups, tiles / csc_ptr / csc_ent / csc_long not touched) and return; a
+ * regnn_ns_hop call with strided = 5, or regnn_nsm_step with csc_pending = 1, finishes the index.
+ * Needs csc_rank (REGNN_EINVAL without it). */
+#define REGNN_NS_CSC_JOB_BUILD 0   /* the whole index (waits for the last workgroup's scan) */
+#define REGNN_NS_CSC_JOB_RANK 1    /* counts + ranks only */
 typedef struct regnn_ns_csc_job {
     int32_t hop;                /* that hop */
     int32_t cap_e;              /* its block's slots: cap_dst * (k + 1) <= 32768 */
@@ -697,6 +707,8 @@ typedef struct regnn_ns_csc_job {
     int32_t* csc_ptr;
     int32_t* csc_ent;
     int32_t* csc_long;
+    int32_t* csc_rank;          /* ABI 50: [cap_e], kind REGNN_NS_CSC_JOB_RANK (else may be NULL) */
+    int32_t kind;               /* ABI 50: REGNN_NS_CSC_JOB_* */
 } regnn_ns_csc_job;
 /* layout (may be NULL; ABI 47): node ids grouped by type -- type t's nodes are the ids
  * [type_off[t], type_off[t + 1]) (equal offsets: a type without nodes), node u's table row is

@@ -805,6 +805,7 @@ struct NsCscJob {
     const int32_t* gsrc; const uint64_t* g2l;
     int32_t* blk_idx; const int32_t* blk_row; const uint8_t* blk_rel;
     int32_t* csc_cnt; int32_t* tiles; int32_t* csc_ptr; int32_t* csc_ent; int32_t* csc_long;
+    int32_t* csc_rank; int kind;           // kind REGNN_NS_CSC_JOB_RANK: counts + ranks only
 };
 
 // The strided transposed index's control words, past everything the CSR path's flag tiles use
@@ -902,11 +903,11 @@ ns_resolve_csc_kernel(NsCscJob J, const int32_t* __restrict__ sizes,
 // only part that reads the dedup table the next batch's sampling overwrites. The second half
 // (csc_scan_place, re_csc_place.h) reads the slot's own buffers only.
 static_assert(kCscPlaceMax == kCscMax && kCscPlaceShort == kCscShort, "re_csc_place.h");
-__global__ void __launch_bounds__(kBlock)
-ns_csc_rank_kernel(const int32_t* __restrict__ gsrc, const uint64_t* __restrict__ g2l,
-                   int32_t* __restrict__ blk_idx, int32_t* __restrict__ csc_cnt,
-                   int32_t* __restrict__ csc_rank, int cap_e) {
-    const int bp = blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void csc_rank_slot(const int32_t* __restrict__ gsrc,
+                                              const uint64_t* __restrict__ g2l,
+                                              int32_t* __restrict__ blk_idx,
+                                              int32_t* __restrict__ csc_cnt,
+                                              int32_t* __restrict__ csc_rank, int cap_e, int bp) {
     if (bp >= cap_e) return;
     const int u = gsrc[bp];
     if (u == -2) return;               // an empty slot of the strided layout
@@ -918,6 +919,13 @@ ns_csc_rank_kernel(const int32_t* __restrict__ gsrc, const uint64_t* __restrict_
         blk_idx[bp] = lid;
     }
     csc_rank[bp] = atomicAdd(csc_cnt + lid, 1);      // integer: exact in any order
+}
+
+__global__ void __launch_bounds__(kBlock)
+ns_csc_rank_kernel(const int32_t* __restrict__ gsrc, const uint64_t* __restrict__ g2l,
+                   int32_t* __restrict__ blk_idx, int32_t* __restrict__ csc_cnt,
+                   int32_t* __restrict__ csc_rank, int cap_e) {
+    csc_rank_slot(gsrc, g2l, blk_idx, csc_cnt, csc_rank, cap_e, blockIdx.x * kBlock + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(kCscPlaceT) ns_csc_place_kernel(CscPlaceArgs A) {
@@ -996,8 +1004,14 @@ __global__ void __launch_bounds__(64 * kNsSumWaves, kNsSumOcc)
 ns_sample_sums_kernel(NsSumArgs A) {
     // the first csc_blocks workgroups build the earlier hop's transposed index (latency-bound:
     // dispatched first, they run beside the sums instead of ahead of them)
+    // kind REGNN_NS_CSC_JOB_RANK: the split build's first half only (ns_csc_rank_kernel's body,
+    // a slot per thread: no wait between workgroups), the placement a launch of its own after
     if (int(blockIdx.x) < A.csc_blocks) {
-        csc_resolve_place<4>(A.csc, A.sizes, A.state, blockIdx.x, A.csc_blocks);
+        if (A.csc.kind == REGNN_NS_CSC_JOB_RANK)
+            csc_rank_slot(A.csc.gsrc, A.csc.g2l, A.csc.blk_idx, A.csc.csc_cnt, A.csc.csc_rank,
+                          A.csc.cap_e, blockIdx.x * (64 * kNsSumWaves) + threadIdx.x);
+        else
+            csc_resolve_place<4>(A.csc, A.sizes, A.state, blockIdx.x, A.csc_blocks);
         return;
     }
     const int bid = blockIdx.x - A.csc_blocks, nbk = gridDim.x - A.csc_blocks;
@@ -1826,6 +1840,23 @@ int regnn_ns_batch(const int64_t* perm, int64_t n_perm, int32_t batch, int32_t r
     return REGNN_OK;
 }
 
+// the split index's second half: every workgroup's own scan and placement
+static int ns_csc_place_launch(int32_t* sizes, int hop, int ce, int k, int32_t* csc_cnt,
+                               int32_t* csc_rank, int32_t* blk_idx, uint8_t* blk_rel,
+                               int32_t* csc_ptr, int32_t* csc_ent, int32_t* csc_long,
+                               hipStream_t stream) {
+    const CscPlaceArgs P{sizes, hop, ce, k + 1, csc_cnt, csc_rank, blk_idx, blk_rel,
+                         csc_ptr, csc_ent, csc_long};
+    const size_t lds = csc_place_lds(ce);
+    static size_t done = 0;
+    if (!nsm::set_lds(reinterpret_cast<const void*>(&ns_csc_place_kernel), lds, &done))
+        return REGNN_EUNSUPPORTED;
+    hipLaunchKernelGGL(ns_csc_place_kernel, dim3(unsigned(csc_place_blocks(ce))),
+                       dim3(kCscPlaceT), lds, stream, P);
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}
+
 int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                  const int32_t* ntype, int32_t num_edge_types, int32_t k, int32_t hop,
                  int64_t* state, int32_t* sizes, int32_t* n_id, int32_t cap_dst,
@@ -1854,13 +1885,19 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
     if (csc && cap_e > kCscMax) return REGNN_EUNSUPPORTED;
     // strided = 4: the split index's first half only (the caller's step finishes it)
     if (strided == 4 && (!csc || !csc_rank || edge_type || lean)) return REGNN_EINVAL;
+    if (strided == 5) {
+        // the split index's second half only (counts + ranks: a sums launch's rank job)
+        if (!csc || !csc_rank || edge_type || lean) return REGNN_EINVAL;
+        return ns_csc_place_launch(sizes, hop, int(cap_e), k, csc_cnt, csc_rank, blk_idx, blk_rel,
+                                   csc_ptr, csc_ent, csc_long, stream);
+    }
     if (strided == 3) {
         // the transposed index only (the part a strided = 2 call left out), on whatever stream
         // the caller runs it: resolve + counts + ranks, scan, placement
         if (!csc || edge_type || lean) return REGNN_EINVAL;
         const int ce = int(cap_e);
         const NsCscJob J{hop, ce, gsrc, g2l, blk_idx, blk_row, blk_rel, csc_cnt, tiles, csc_ptr,
-                         csc_ent, csc_long};
+                         csc_ent, csc_long, nullptr, REGNN_NS_CSC_JOB_BUILD};
         hipLaunchKernelGGL(ns_resolve_csc_kernel, dim3(unsigned(csc_blocks(cap_e))),
                            dim3(kCscScanT), 0, stream, J, sizes, state);
         REGNN_LAUNCH_CHECK();
@@ -1897,22 +1934,14 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                                dim3(kBlock), 0, stream, gsrc, g2l, blk_idx, csc_cnt, csc_rank, ce);
             REGNN_LAUNCH_CHECK();
             if (strided == 4) return REGNN_OK;
-            const CscPlaceArgs P{sizes, hop, ce, k + 1, csc_cnt, csc_rank, blk_idx, blk_rel,
-                                 csc_ptr, csc_ent, csc_long};
-            const size_t lds = csc_place_lds(ce);
-            static size_t done = 0;
-            if (!nsm::set_lds(reinterpret_cast<const void*>(&ns_csc_place_kernel), lds, &done))
-                return REGNN_EUNSUPPORTED;
-            hipLaunchKernelGGL(ns_csc_place_kernel, dim3(unsigned(csc_place_blocks(ce))),
-                               dim3(kCscPlaceT), lds, stream, P);
-            REGNN_LAUNCH_CHECK();
-            return REGNN_OK;
+            return ns_csc_place_launch(sizes, hop, ce, k, csc_cnt, csc_rank, blk_idx, blk_rel,
+                                       csc_ptr, csc_ent, csc_long, stream);
         }
         if (csc && !edge_type) {
             // the transposed index by many blocks in one launch: resolve + counts + ranks, the
             // last block's scan, every block's placement
             const NsCscJob J{hop, ce, gsrc, g2l, blk_idx, blk_row, blk_rel, csc_cnt, tiles,
-                             csc_ptr, csc_ent, csc_long};
+                             csc_ptr, csc_ent, csc_long, nullptr, REGNN_NS_CSC_JOB_BUILD};
             hipLaunchKernelGGL(ns_resolve_csc_kernel, dim3(unsigned(csc_blocks(cap_e))),
                                dim3(kCscScanT), 0, stream, J, sizes, state);
             REGNN_LAUNCH_CHECK();
@@ -2019,11 +2048,16 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
             !csc->csc_cnt || !csc->tiles || !csc->csc_ptr || !csc->csc_ent || !csc->csc_long ||
             csc->hop < 0 || csc->hop >= hop || csc->cap_e <= 0)
             return REGNN_EINVAL;
+        const bool rank = csc->kind == REGNN_NS_CSC_JOB_RANK;
+        if (!rank && csc->kind != REGNN_NS_CSC_JOB_BUILD) return REGNN_EINVAL;
+        if (rank && !csc->csc_rank) return REGNN_EINVAL;
         if (csc->cap_e > kCscMax) return REGNN_EUNSUPPORTED;
         A.csc = NsCscJob{csc->hop, csc->cap_e, csc->gsrc, csc->g2l, csc->blk_idx, csc->blk_row,
                          csc->blk_rel, csc->csc_cnt, csc->tiles, csc->csc_ptr, csc->csc_ent,
-                         csc->csc_long};
-        A.csc_blocks = csc_blocks(csc->cap_e);
+                         csc->csc_long, csc->csc_rank, csc->kind};
+        // the rank job: a slot per thread of the sums launch's 256-thread workgroups
+        A.csc_blocks = rank ? (csc->cap_e + 64 * kNsSumWaves - 1) / (64 * kNsSumWaves)
+                            : csc_blocks(csc->cap_e);
     }
     // REGNN_NS_SUM_BLOCKS: N > 0 caps the grid at N blocks, < 0: a block per row group whatever
     // their number; 0 / unset: no more blocks than the GPU holds at once, each taking the same

@@ -144,6 +144,9 @@ class DeviceSampler:
         # head launch (FusedStep.defer_csc asks for it); csc_deferred[h]: the latest run_hops did
         self.csc_defer = [False] * len(self.sizes_k)
         self.csc_deferred = [False] * len(self.sizes_k)
+        # csc_ride: a strided hop's counts + ranks ride the next hop's sums launch where one
+        # follows (CSC_RIDE when the sampler is built; run_hops)
+        self.csc_ride = CSC_RIDE["mode"] != "off"
         # strided: every hop's block in the fixed-stride layout (row i at i (k + 1), regnn_ns_hop
         # strided) -- the two-layer fused step's layout; False: the CSR layout the module path,
         # exact_adjs and the PyG-style API read
@@ -222,7 +225,7 @@ class DeviceSampler:
         # samples its outer hop strided with the input sums while hop 0 stays CSR
         hs = lambda h: strided if self.hop_strided[h] is None else self.hop_strided[h]  # noqa: E731
         rg = self.rg
-        deferred = -1
+        deferred, ride_place = -1, None
         for h, k in enumerate(self.sizes_k):
             b, blk = self.hop_bufs[h], self.blocks[h]
             sh = hs(h)
@@ -248,8 +251,14 @@ class DeviceSampler:
                            L.ptr(et), L.ptr(eo), ts["tables"], ts["T"], ts["K"],
                            L.ptr(ts["s_agg"]), L.ptr(ts["s_w"]), L.ptr(ts["u_self"]),
                            L.ptr(ts["u_rel"]),
-                           ctypes.addressof(self._csc_job(h - 1)) if deferred == h - 1 else None,
+                           ctypes.addressof(self._csc_job(h - 1, ride_place is not None))
+                           if deferred == h - 1 else None,
                            None if lay is None else ctypes.addressof(lay), L.stream())
+                if ride_place is not None and ride_place[2]:
+                    # the ranks rode this launch: hop h - 1's placement follows it on this stream
+                    # (the index is complete when run_hops returns)
+                    self._hop_call(ride_place[0], ride_place[1], meta_only, 5, split=True)
+                deferred, ride_place = -1, None
                 self.meta_fresh[h] = not skip
                 self.sums_fresh[h] = True
                 continue
@@ -268,6 +277,12 @@ class DeviceSampler:
             defer = (not fork and not later and sh and CSC_FUSE["mode"] != "off" and
                      self.csc[h] is not None and self.edge_meta[h] is None and
                      h + 1 < len(self.sizes_k) and self._sums_path(h + 1, hs(h + 1), meta_only))
+            # the split build's first half (counts + ranks) in leading workgroups of the next
+            # hop's sums launch (CSC_RIDE; regnn_ns_csc_job kind 1): this call stops after the
+            # de-duplication; the placement follows the sums launch, or is the head launch's
+            ride = (split and not defer and sh and self.csc_ride and
+                    self.csc[h] is not None and self.edge_meta[h] is None and
+                    h + 1 < len(self.sizes_k) and self._sums_path(h + 1, hs(h + 1), meta_only))
             L.call("regnn_ns_hop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(self.etype_csr),
                    L.ptr(self.ntype), self.num_edge_types, k, h, L.ptr(self.state),
                    L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h], L.ptr(self.g2l),
@@ -280,8 +295,9 @@ class DeviceSampler:
                      if self.edge_meta[h] is not None else (None, None, None)),
                    int(meta_only and self.meta_only[h] and self.edge_meta[h] is not None),
                    *self._csc_args(h, split),
-                   4 if later else 2 if fork or defer else int(sh), L.stream())
-            deferred = h if defer else -1
+                   2 if ride or fork or defer else 4 if later else int(sh), L.stream())
+            deferred = h if defer or ride else -1
+            ride_place = (h, k, not later) if ride else None
             if fork:
                 csc_stream.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(csc_stream):
@@ -295,19 +311,20 @@ class DeviceSampler:
         return (self.typed_sums[h] is not None and strided and meta_only and self.meta_only[h]
                 and self.edge_meta[h] is not None)
 
-    def _csc_job(self, h):
-        """regnn_ns_csc_job of hop h's transposed index (its buffers are fixed: built once)"""
-        job = self._csc_jobs.get(h)
+    def _csc_job(self, h, rank=False):
+        """regnn_ns_csc_job of hop h's transposed index (its buffers are fixed: built once);
+        rank: the counts + ranks job (kind 1) instead of the whole build"""
+        job = self._csc_jobs.get((h, rank))
         if job is None:
             b, blk = self.hop_bufs[h], self.blocks[h]
             cnt, cptr, cent, clong = self.csc[h]
-            job = self._csc_jobs[h] = _NsCscJob(
+            job = self._csc_jobs[(h, rank)] = _NsCscJob(
                 h, blk.csr_idx.numel(), L.ptr(b["gsrc"]), L.ptr(self.g2l), L.ptr(blk.csr_idx),
                 L.ptr(blk.row), L.ptr(blk.rel), L.ptr(cnt), L.ptr(b["tiles"]), L.ptr(cptr),
-                L.ptr(cent), L.ptr(clong))
+                L.ptr(cent), L.ptr(clong), L.ptr(self.csc_rank[h]) if rank else None, int(rank))
         return job
 
-    def _hop_call(self, h, k, meta_only, mode):
+    def _hop_call(self, h, k, meta_only, mode, split=False):
         rg, b, blk = self.rg, self.hop_bufs[h], self.blocks[h]
         L.call("regnn_ns_hop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(self.etype_csr),
                L.ptr(self.ntype), self.num_edge_types, k, h, L.ptr(self.state),
@@ -319,7 +336,7 @@ class DeviceSampler:
                *((L.ptr(self.local), L.ptr(self.edge_meta[h][0]), L.ptr(self.edge_meta[h][1]))
                  if self.edge_meta[h] is not None else (None, None, None)),
                int(meta_only and self.meta_only[h] and self.edge_meta[h] is not None),
-               *self._csc_args(h, False), mode, L.stream())
+               *self._csc_args(h, split), mode, L.stream())
 
     def set_seed(self, base_seed, epoch, batch_idx):
         """host-driven batches (the PyG-style iterator): seed words + a fresh dedup stamp."""
@@ -426,7 +443,8 @@ class _NsCscJob(ctypes.Structure):
     """regnn_ns_csc_job (include/regnn_hip.h)."""
     _fields_ = [("hop", ctypes.c_int32), ("cap_e", ctypes.c_int32), ("gsrc", _P), ("g2l", _P),
                 ("blk_idx", _P), ("blk_row", _P), ("blk_rel", _P), ("csc_cnt", _P),
-                ("tiles", _P), ("csc_ptr", _P), ("csc_ent", _P), ("csc_long", _P)]
+                ("tiles", _P), ("csc_ptr", _P), ("csc_ent", _P), ("csc_long", _P),
+                ("csc_rank", _P), ("kind", ctypes.c_int32)]
 
 
 class _NsmAdam(ctypes.Structure):
@@ -551,9 +569,18 @@ CSC_FUSE = {"mode": os.environ.get("REGNN_NS_CSC_FUSE", "off")}
 # placement); "off": the single launch whose last block scans while the others spin (A/B)
 CSC_SPLIT = {"mode": os.environ.get("REGNN_NS_CSC_SPLIT", "on")}
 # "on": the fused trainer's hop 0 runs the split build's first launch only and the step's head
-# launch finishes the index on CUs it leaves idle (regnn_nsm_work csc_pending); "off" (default):
-# both launches on the sampler's queue. DESIGN section 4b has the measurements behind the default
-CSC_DEFER = {"mode": os.environ.get("REGNN_NS_CSC_DEFER", "off")}
+# launch finishes the index on CUs it leaves idle (regnn_nsm_work csc_pending); "off": the
+# placement on the sampler's queue; "auto" (default): "on" where hop 0's counts + ranks ride the
+# sums launch (CSC_RIDE: the placement would otherwise be one more launch after the sums, and the
+# sampler's chain per batch ends with the sums launch instead), else "off" (with the rank launch
+# of its own the deferral measured within noise). DESIGN section 4b has the measurements
+CSC_DEFER = {"mode": os.environ.get("REGNN_NS_CSC_DEFER", "auto")}
+# "on" (default): where a strided hop's split build is followed by the sums launch (the fused
+# trainer's hop 0), its counts + ranks run in leading workgroups of that launch instead of a
+# launch of their own (regnn_ns_csc_job kind 1: a slot per thread, no wait), and the placement
+# follows the sums launch (or rides the head launch, CSC_DEFER); "off": the rank launch of its
+# own ahead of the sums. Every other hop sequence is the same either way
+CSC_RIDE = {"mode": os.environ.get("REGNN_NS_CSC_RIDE", "on")}
 # the head launch's dynamic-LDS limit (re_nsm2.hip): the deferred half's LDS must fit under it
 _HEAD_LDS_MAX = 160 * 1024 - 2560
 # the fused engine's sampling lookahead G: 2G sampler slots, each step samples the batch trained
@@ -882,15 +909,20 @@ class FusedStep:
     def defer_csc(self):
         """hop 0's transposed index finished by this step's head launch instead of the sampler's
         queue (CSC_DEFER): the sampler's strided hop 0 then writes counts and ranks only
-        (regnn_ns_hop strided = 4) and the step runs with csc_pending. Returns whether it
+        (regnn_ns_hop strided = 4; with CSC_RIDE the outer hop's sums launch writes them and
+        hop 0 stops after its de-duplication) and the step runs with csc_pending. Returns whether it
         applies: the two-layer step over strided blocks, the split build, neither CSC_FORK nor
         CSC_FUSE, and the scan's LDS under the head launch's limit (else both launches stay on
         the sampler's queue). No path here can raise the index's error word (index_errors)."""
         s, W = self.sampler, self.W
         ce = s.blocks[0].csr_idx.numel()
+        mode = CSC_DEFER["mode"]
+        if mode == "auto":                     # where hop 0's ranks ride the outer hop's sums launch
+            mode = "on" if (s.csc_ride and len(s.sizes_k) > 1 and
+                            s._sums_path(1, True, True)) else "off"
         ok = (self.two_layer and s.strided and s.csc[0] is not None and
               s.edge_meta[0] is None and
-              CSC_SPLIT["mode"] != "off" and CSC_DEFER["mode"] != "off" and
+              CSC_SPLIT["mode"] != "off" and mode != "off" and
               CSC_FORK["mode"] == "off" and CSC_FUSE["mode"] == "off" and
               (ce + 64) * 4 <= _HEAD_LDS_MAX and
               # the index's grid row is no wider than the head's own (ceil(cap0 / 16) blocks of
@@ -1235,7 +1267,8 @@ class NSTrainer:
         if self.adam_fused:
             for fs in (self.fused_slots if self.pipelined else [self.fused]):
                 fs.attach_adam(self.opt, self.flat)
-        # the fused engine only, where CSC_DEFER asks for it (off by default): each slot's head
+        # the fused engine only, where CSC_DEFER asks for it (by default where hop 0's ranks ride
+        # the sums launch): each slot's head
         # launch finishes the transposed index its sampler left at counts + ranks
         if self.fused is not None:
             for fs in (self.fused_slots if self.pipelined else [self.fused]):
