@@ -735,6 +735,28 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
                             int32_t* u_rel, const regnn_ns_csc_job* csc,
                             const regnn_ns_type_layout* layout, hipStream_t stream);
 
+/* regnn_ns_hop_typed_sums over input tables stored in dtype (added under ABI 50: a new symbol, no
+ * struct or existing prototype moves). Replaces the same reference lines (the raw-feature gather of
+ * mag/regnn_ns.py:300-326 + mag/regnn_layers.py:110-144 for layer 0) when x_dict is kept in
+ * bfloat16. dtype REGNN_F32: regnn_ns_hop_typed_sums itself (which forwards here). dtype
+ * REGNN_BF16: tables[t] rows are K = 128 bf16 (256 bytes; each lane reads its 4 columns as one
+ * 8-byte load and widens them with a 16-bit shift); the sampling, the slots, the order of the
+ * additions and every output -- all fp32 -- are those of the fp32 kernels, so the call gives the
+ * same bits as the fp32 entry on the widened table (x.bfloat16().float()), u_self the widened rows
+ * themselves. Every parameter but tables / dtype as in regnn_ns_hop_typed_sums.
+ * REGNN_EINVAL before any launch: another dtype, a NULL table, a table base not 16-byte aligned
+ * (either dtype); REGNN_EUNSUPPORTED as for the fp32 entry (K != 128, n_types > 4, k outside
+ * 1..63). */
+int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                               const int32_t* ntype, int32_t num_edge_types, int32_t k,
+                               int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
+                               int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
+                               const int64_t* local, int32_t* edge_type, int64_t* edge_off,
+                               const void* const* tables, int32_t dtype, int32_t n_types,
+                               int32_t K, float* s_agg, float* s_w, float* u_self, int32_t* u_rel,
+                               const regnn_ns_csc_job* csc, const regnn_ns_type_layout* layout,
+                               hipStream_t stream);
+
 /* Backward of a sampled block's aggregation y[v] = out_scale[v] sum_e rel_table[rel_e] x[idx_e]
  * (+ bias) over rows v < n_rows (the forward is regnn_spmm_fwd on the block):
  *   gx[idx_e] += rel_table[rel_e] * out_scale[v] * g[v]   (gx zero-filled by the caller; hardware

@@ -950,7 +950,7 @@ struct NsSumArgs {
     const int32_t* n_id; int32_t* sizes; int hop; int cap; int k;
     int64_t* state;
     int32_t* scnt; uint8_t* blk_rel; float* inv; int32_t* e_type; int64_t* e_off;
-    const float* xt[8]; int T;
+    const void* xt[8]; int T;               // the tables' rows: float or bf16_t (the kernel's XT)
     float* s_agg; float* s_w; float* u_self; int32_t* u_rel;
     NsCscJob csc; int csc_blocks;          // an earlier hop's transposed index (csc_blocks > 0)
     // DERIVE (node ids grouped by type, regnn_ns_type_layout): type q's first node id (q = 1..3;
@@ -973,14 +973,36 @@ __device__ __forceinline__ int ns_type_first(const NsSumArgs& A, int t) {
     return o;
 }
 
-template <int NT>
-__device__ __forceinline__ const float* pick_tab(const NsSumArgs& A, int t) {
-    const float* r = A.xt[0];
+template <int NT, typename XT>
+__device__ __forceinline__ const XT* pick_tab(const NsSumArgs& A, int t) {
+    const void* r = A.xt[0];
 #pragma unroll
     for (int q = 1; q < NT; ++q)
         if (t == q) r = A.xt[q];
-    return r;
+    return static_cast<const XT*>(r);
 }
+
+// A lane's 4 columns of a table row as they stay in registers until they are added (float: a
+// float4; bf16_t: one 8-byte load, 2 VGPRs) and their widening to fp32: bf16 -> fp32 is the 16-bit
+// shift, so a bf16 table gives the bits the float kernel gives on the widened table
+template <typename XT> struct NsRow;
+template <> struct NsRow<float> {
+    using V = float4;
+    __device__ __forceinline__ static V load(const float* p) {
+        return *reinterpret_cast<const float4*>(p);
+    }
+    __device__ __forceinline__ static const float4& widen(const V& v) { return v; }
+};
+template <> struct NsRow<bf16_t> {
+    using V = uint2;
+    __device__ __forceinline__ static V load(const bf16_t* p) {
+        return *reinterpret_cast<const uint2*>(p);
+    }
+    __device__ __forceinline__ static float4 widen(const V& v) {
+        return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u),
+                           __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+    }
+};
 
 constexpr int kNsSumK = 128;               // input row width of the sums kernel
 // entries' rows in flight per lane (32 lanes per row: two rounds of 11 for a fan-out of 20). All
@@ -989,8 +1011,15 @@ constexpr int kNsSumK = 128;               // input row width of the sums kernel
 #ifndef REGNN_NS_SUM_UN32
 #define REGNN_NS_SUM_UN32 11
 #endif
-template <int G>
-constexpr int ns_sum_un() { return G == 32 ? REGNN_NS_SUM_UN32 : 11; }
+// bf16 rows hold half the registers each (REGNN_NS_SUM_UN32_BF16: the bf16 kernels' own setting,
+// at the same occupancy bound; DESIGN 4b has both measurements)
+#ifndef REGNN_NS_SUM_UN32_BF16
+#define REGNN_NS_SUM_UN32_BF16 11
+#endif
+template <int G, typename XT>
+constexpr int ns_sum_un() {
+    return G != 32 ? 11 : sizeof(XT) == 2 ? REGNN_NS_SUM_UN32_BF16 : REGNN_NS_SUM_UN32;
+}
 constexpr int kNsSumOcc = REGNN_NS_SUM_UN32 > 11 ? 3 : 4;   // waves per SIMD the registers allow
 constexpr int kNsSumWaves = 4;             // waves per block (256 threads: they fit beside the
                                            // model's kernels on a shared CU)
@@ -998,8 +1027,10 @@ constexpr int kNsSumWaves = 4;             // waves per block (256 threads: they
 // DERIVE: a slot's source type, table row and relation come from its node id, the type offsets
 // and the pair table (no etype / ntype / local loads: three random line transactions per slot
 // and one level of the dependent chain less); the same values, so the same bits in every output.
-// The per-slot meta (blk_rel / e_type / e_off) is written only when blk_rel is not NULL
-template <int G, int NT, bool DERIVE>
+// The per-slot meta (blk_rel / e_type / e_off) is written only when blk_rel is not NULL.
+// XT: the tables' storage type (float, or bf16_t: 256-byte rows widened on use); every sum, every
+// output and the order of the additions are the same for both
+template <int G, int NT, bool DERIVE, typename XT>
 __global__ void __launch_bounds__(64 * kNsSumWaves, kNsSumOcc)
 ns_sample_sums_kernel(NsSumArgs A) {
     // the first csc_blocks workgroups build the earlier hop's transposed index (latency-bound:
@@ -1016,7 +1047,7 @@ ns_sample_sums_kernel(NsSumArgs A) {
     }
     const int bid = blockIdx.x - A.csc_blocks, nbk = gridDim.x - A.csc_blocks;
     constexpr int K = kNsSumK;
-    constexpr int kNsSumUN = ns_sum_un<G>();
+    constexpr int kNsSumUN = ns_sum_un<G, XT>();
     constexpr int TPW = 64 / G;                // rows per wave
     constexpr int H = G == 64 ? 2 : 1;         // lane groups of 32 per row (each a float4 column)
     __shared__ int wsum[kNsSumWaves * TPW];
@@ -1136,14 +1167,14 @@ ns_sample_sums_kernel(NsSumArgs A) {
         float4 xs = make_float4(0.f, 0.f, 0.f, 0.f);
         int rs = -1;
         for (int j0 = 0; j0 < ne; j0 += H * kNsSumUN) {
-            float4 x[kNsSumUN];
+            typename NsRow<XT>::V x[kNsSumUN];
 #pragma unroll
             for (int u = 0; u < kNsSumUN; ++u) {
                 const int j = j0 + H * u + h;
                 const int jj = j < ne ? j : ne - 1;  // padding: a valid row, loaded, not added
                 const int tj = __shfl(st, jj, G);
                 const int64_t lo = __shfl(slo, jj, G);
-                x[u] = *reinterpret_cast<const float4*>(pick_tab<NT>(A, tj) + lo * K + 4 * l);
+                x[u] = NsRow<XT>::load(pick_tab<NT, XT>(A, tj) + lo * K + 4 * l);
             }
             // (each entry's type / relation shuffled again here: arrays of them held across the
             // loads cost the registers that keep every row in flight)
@@ -1153,8 +1184,9 @@ ns_sample_sums_kernel(NsSumArgs A) {
                 const int jj = j < ne ? j : ne - 1;
                 const int tj = __shfl(st, jj, G), rj = __shfl(sr, jj, G);
                 if (j >= ne) continue;
+                const auto& xv = NsRow<XT>::widen(x[u]);
                 if (rj >= A.n_et) {                // the self loop (one per row)
-                    xs = x[u];
+                    xs = xv;
                     rs = rj;
                     continue;
                 }
@@ -1163,8 +1195,8 @@ ns_sample_sums_kernel(NsSumArgs A) {
                     if (tt != tj) continue;
                     ws[tt] += 1.f;
                     rt[tt] = rj;
-                    racc[tt].x += x[u].x; racc[tt].y += x[u].y;
-                    racc[tt].z += x[u].z; racc[tt].w += x[u].w;
+                    racc[tt].x += xv.x; racc[tt].y += xv.y;
+                    racc[tt].z += xv.z; racc[tt].w += xv.w;
                 }
             }
         }
@@ -1999,6 +2031,22 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
                             int32_t n_types, int32_t K, float* s_agg, float* s_w, float* u_self,
                             int32_t* u_rel, const regnn_ns_csc_job* csc,
                             const regnn_ns_type_layout* layout, hipStream_t stream) {
+    return regnn_ns_hop_typed_sums_dt(ptr, idx, etype, ntype, num_edge_types, k, hop, state, sizes,
+                                      n_id, cap_dst, scnt, blk_rel, inv, local, edge_type, edge_off,
+                                      reinterpret_cast<const void* const*>(tables), REGNN_F32,
+                                      n_types, K, s_agg, s_w, u_self, u_rel, csc, layout, stream);
+}
+
+int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                               const int32_t* ntype, int32_t num_edge_types, int32_t k,
+                               int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
+                               int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
+                               const int64_t* local, int32_t* edge_type, int64_t* edge_off,
+                               const void* const* tables, int32_t dtype, int32_t n_types,
+                               int32_t K, float* s_agg, float* s_w, float* u_self, int32_t* u_rel,
+                               const regnn_ns_csc_job* csc, const regnn_ns_type_layout* layout,
+                               hipStream_t stream) {
+    if (dtype != REGNN_F32 && dtype != REGNN_BF16) return REGNN_EINVAL;
     if (!ptr || !idx || !state || !sizes || !n_id || !scnt || !inv || !tables || !s_agg ||
         !s_w || !u_self || !u_rel || cap_dst <= 0 || hop < 0 || hop > 6 || num_edge_types < 0)
         return REGNN_EINVAL;
@@ -2076,30 +2124,42 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
             n_cu = 256;
         return n_cu * (4 * kNsSumOcc / kNsSumWaves);
     }();
+    // bf16 rows: half the resident blocks (mag-10x: 416 blocks of four rounds). Beside the model's
+    // kernels the 832-block grid measured 97.2-97.8 us per step on bf16 tables against 94.0-94.9
+    // on fp32 ones, 416 blocks 93.7-94.4 (fp32 at 416: 95.2-95.7); DESIGN 4b
+    const int held = dtype == REGNN_BF16 ? (resident + 1) / 2 : resident;
     auto grid = [&](int rows_per_block) {
         const int g = (cap_dst + rows_per_block - 1) / rows_per_block;
         int nb = g;
         if (sum_blocks > 0) {
             nb = sum_blocks < g ? sum_blocks : g;
-        } else if (sum_blocks == 0 && g > resident) {
-            const int rounds = (g + resident - 1) / resident;
+        } else if (sum_blocks == 0 && g > held) {
+            const int rounds = (g + held - 1) / held;
             nb = (g + rounds - 1) / rounds;
         }
         return dim3(unsigned(A.csc_blocks + nb));
     };
     const bool derive = layout != nullptr;
-    if (k + 1 <= 32 && derive)         // two rows per wave (32 lanes each): sums in slot order
-        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, true>), grid(2 * kNsSumWaves),
+    // a kernel per storage type (a runtime dtype would cost the float kernels registers)
+#define NS_SUMS_LAUNCH(XT)                                                                     \
+    if (k + 1 <= 32 && derive)         /* two rows per wave (32 lanes each): slot order */      \
+        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, true, XT>), grid(2 * kNsSumWaves),    \
+                           dim3(64 * kNsSumWaves), 0, stream, A);                              \
+    else if (k + 1 <= 32)                                                                      \
+        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, false, XT>), grid(2 * kNsSumWaves),   \
+                           dim3(64 * kNsSumWaves), 0, stream, A);                              \
+    else if (derive)                                                                           \
+        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, true, XT>), grid(kNsSumWaves),        \
+                           dim3(64 * kNsSumWaves), 0, stream, A);                              \
+    else                                                                                       \
+        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, false, XT>), grid(kNsSumWaves),       \
                            dim3(64 * kNsSumWaves), 0, stream, A);
-    else if (k + 1 <= 32)
-        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, false>), grid(2 * kNsSumWaves),
-                           dim3(64 * kNsSumWaves), 0, stream, A);
-    else if (derive)
-        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, true>), grid(kNsSumWaves),
-                           dim3(64 * kNsSumWaves), 0, stream, A);
-    else
-        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, false>), grid(kNsSumWaves),
-                           dim3(64 * kNsSumWaves), 0, stream, A);
+    if (dtype == REGNN_BF16) {
+        NS_SUMS_LAUNCH(bf16_t)
+    } else {
+        NS_SUMS_LAUNCH(float)
+    }
+#undef NS_SUMS_LAUNCH
     REGNN_LAUNCH_CHECK();
     return REGNN_OK;
 }

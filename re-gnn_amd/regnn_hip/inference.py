@@ -100,6 +100,11 @@ def exchange_rows(x_loc, bounds, rank, world, group=None):
     return torch.cat([buf[r * m:r * m + rows[r]] for r in range(world)], 0)
 
 
+# rows of a bf16 input table widened to fp32 at a time in ShardedInference.input (the fp32
+# temporary is at most this many rows, never the table)
+BF16_CHUNK_ROWS = 1 << 20
+
+
 class ShardedInference:
     """The rank-local half of REGNN.inference: holds this rank's RowBlock and steps the layers.
 
@@ -130,7 +135,9 @@ class ShardedInference:
     def input(self, x_dict, layer=0):
         """group_input for the own rows (mag/regnn_ns.py:300-326). Node ids are type-contiguous
         (the mag node numbering), so each type's Linear is one GEMM over its row range written
-        in place; otherwise the model's generic group_input."""
+        in place; otherwise the model's generic group_input (fp32 tables only). bf16 tables
+        (x.bfloat16(): exact to widen) go through the same GEMMs BF16_CHUNK_ROWS rows at a time,
+        each chunk widened to fp32 first: the result is that of the widened table."""
         m = self.model
         nt = self.node_type[self.r0:self.r1]
         x = None
@@ -146,7 +153,14 @@ class ShardedInference:
                 xt = x_dict[t]
                 lin = m.lins[str(t)]
                 ar = torch.arange(l0, l0 + (b - a), device=loc.device)
-                if bool((loc[a:b] == ar).all()):                  # contiguous local ids
+                if xt.dtype == torch.bfloat16:
+                    rows = None if bool((loc[a:b] == ar).all()) else loc[a:b]
+                    for c in range(a, b, BF16_CHUNK_ROWS):
+                        d = min(b, c + BF16_CHUNK_ROWS)
+                        xc = (xt[l0 + c - a:l0 + d - a] if rows is None
+                              else xt[rows[c - a:d - a]]).float()
+                        torch.addmm(lin.bias, xc, lin.weight.t(), out=x[c:d])
+                elif bool((loc[a:b] == ar).all()):                # contiguous local ids
                     torch.addmm(lin.bias, xt[l0:l0 + (b - a)], lin.weight.t(), out=x[a:b])
                 else:
                     torch.addmm(lin.bias, xt[loc[a:b]], lin.weight.t(), out=x[a:b])

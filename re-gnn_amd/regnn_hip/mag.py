@@ -386,6 +386,10 @@ class REGNN(torch.nn.Module):
         MFMA launch over the type-sorted rows (ops.typed_linear). Other shapes: one GEMM against
         all types' weights + a per-node pick."""
         tabs = self._type_tables(x_dict)
+        if any(torch.is_tensor(x) and x.dtype == torch.bfloat16 for x in x_dict.values()):
+            # (no upcast of a whole table here, and the gather-fused Linear reads fp32 rows)
+            raise ValueError("bf16 input tables are read by the NS sampler's sums launch only "
+                             "(NSTrainer / FusedStep with pre_sums); group_input needs fp32 tables")
         on_dev = tabs is not None and all(t is None or (t.is_cuda and t.dtype == torch.float32
                                                         and t.dim() == 2) for t in tabs)
         widths = {t.shape[1] for t in tabs if t is not None} if on_dev else set()
@@ -449,7 +453,8 @@ class REGNN(torch.nn.Module):
                 self.self_loop_type != 2):
             return False
         tabs = self._type_tables(x_dict)
-        return (tabs is not None and ops.ns_typed_agg_ok(tabs) and
+        # (bf16 tables: only with the sampler's input sums, which NSTrainer then insists on)
+        return (tabs is not None and ops.ns_typed_agg_ok(tabs, pre_sums=True) and
                 self.convs[0].relation_weight.numel() <= 256)
 
     def _wide_epi(self, blk):
@@ -485,7 +490,9 @@ class REGNN(torch.nn.Module):
         if blk is None or getattr(blk, "inv", None) is None:
             return None
         tabs = self._type_tables(x_dict)
-        if tabs is None or not ops.ns_typed_agg_ok(tabs) or not n_id.is_cuda:
+        # (with blk.pre_sums the tables are never read here: they may be bf16)
+        pre = getattr(blk, "pre_sums", None) is not None
+        if tabs is None or not ops.ns_typed_agg_ok(tabs, pre_sums=pre) or not n_id.is_cuda:
             return None
         conv = self.convs[0]
         if conv.relation_weight.numel() > 256:

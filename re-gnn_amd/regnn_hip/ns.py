@@ -244,11 +244,13 @@ class DeviceSampler:
                         (mode == "off" or torch.cuda.is_current_stream_capturing()))
                 rel, et, eo = (None, None, None) if skip else (blk.rel, *self.edge_meta[h])
                 with timed("ns_typed_sums"):
-                    L.call("regnn_ns_hop_typed_sums", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
+                    # the tables' storage type (ts["dtype"]: fp32 unless the x_dict is bf16)
+                    L.call("regnn_ns_hop_typed_sums_dt", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
                            L.ptr(self.etype_csr), L.ptr(self.ntype), self.num_edge_types, k, h,
                            L.ptr(self.state), L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h],
                            L.ptr(b["scnt"]), L.ptr(rel), L.ptr(blk.inv), L.ptr(self.local),
-                           L.ptr(et), L.ptr(eo), ts["tables"], ts["T"], ts["K"],
+                           L.ptr(et), L.ptr(eo), ts["tables"], ts.get("dtype", L.F32_CODE),
+                           ts["T"], ts["K"],
                            L.ptr(ts["s_agg"]), L.ptr(ts["s_w"]), L.ptr(ts["u_self"]),
                            L.ptr(ts["u_rel"]),
                            ctypes.addressof(self._csc_job(h - 1, ride_place is not None))
@@ -470,7 +472,10 @@ def fused_unsupported(model, x_dict):
     reference configuration of mag/regnn_ns.py: model 'regcn', self_loop_type 2, use_norm 'ln',
     feats_type != 2, hidden 64, equal input widths 64 / 128, <= 8 node types, 2..4 layers,
     <= 448 classes; residual on every conv or on none, and residual in the two-layer form only
-    (2 layers, <= TWO_LAYER_MAX_CLASSES classes; FusedStep also checks the hop-0 capacity)."""
+    (2 layers, <= TWO_LAYER_MAX_CLASSES classes; FusedStep also checks the hop-0 capacity).
+    The input tables are contiguous and of one dtype: fp32, or bf16 at width 128 with <= 4 node
+    types -- bf16 rows are read by the sampler's sums launch alone (regnn_ns_hop_typed_sums_dt),
+    so FusedStep further needs its pre_sums conditions and raises where they do not hold."""
     if getattr(model, "model", None) != "regcn" or getattr(model, "feats_type", 3) == 2:
         return "model is not the feats_type-3 regcn"
     if model.self_loop_type != 2:
@@ -493,15 +498,52 @@ def fused_unsupported(model, x_dict):
     if len(dims) != 1 or dims.pop() not in (64, 128):
         return "input widths must be equal, 64 or 128"
     K = int(x_dict[keys[0]].shape[1])
+    dts = {x_dict[k].dtype for k in keys}
+    if len(dts) != 1:
+        return "inputs must share one dtype (all fp32 or all bf16)"
+    dt = dts.pop()
+    if (dt not in (torch.float32, torch.bfloat16) or
+            any(not x_dict[k].is_contiguous() for k in keys)):
+        return "inputs must be contiguous fp32 (or bf16: width 128, <= 4 node types)"
+    if dt == torch.bfloat16 and (K != 128 or len(keys) > 4):
+        return "bf16 inputs need width 128 and <= 4 node types (the sampler's sums launch)"
     if len(keys) * (K + 1) > 600:              # regnn_nsm_step's composed-map bound
         return f"{len(keys)} node types x input width {K} exceed the fused step's tables"
-    if any(x_dict[k].dtype != torch.float32 or not x_dict[k].is_contiguous() for k in keys):
-        return "inputs must be contiguous fp32"
     if model.out_lin.weight.shape[0] > 448 or model.out_lin.weight.shape[1] != 64:
         return "out_lin must be 64 -> <= 448"
     if res[0] and (len(convs) != 2 or model.out_lin.weight.shape[0] > TWO_LAYER_MAX_CLASSES):
         return _RESIDUAL_TWO_LAYER
     return None
+
+
+def fused_bf16_unsupported(model, sampler, x_dict):
+    """why the fused step cannot read these bf16 input tables over this sampler's blocks (None: it
+    can, or the tables are fp32). bf16 rows are read by the sampler's sums launch alone
+    (regnn_ns_hop_typed_sums_dt; regnn_nsm_work.pre_sums): the step's own gathers (agg0) read
+    fp32, so every condition of the input sums must hold. Changes nothing of the sampler."""
+    keys = sorted(x_dict)
+    if x_dict[keys[0]].dtype != torch.bfloat16:
+        return None
+    T, K = len(keys), int(x_dict[keys[0]].shape[1])
+    two_layer = (len(model.convs) == 2 and
+                 model.out_lin.weight.shape[0] <= TWO_LAYER_MAX_CLASSES and
+                 sampler.blocks[0].csr_idx.numel() <= TWO_LAYER_MAX_EDGES)
+    if PRE_SUMS["mode"] == "off":
+        missing = "PRE_SUMS is off"
+    elif not two_layer:
+        missing = "not the two-layer step"
+    elif K != 128 or T > 4:
+        missing = "width 128 and <= 4 node types"
+    elif STRIDED["mode"] == "off" or LEAN_LAST_HOP["mode"] == "off":
+        missing = "the blocks are not strided (STRIDED / LEAN_LAST_HOP off)"
+    elif max(sampler.sizes_k) > 63:
+        missing = "a fan-out above 63"
+    elif REL_SLOTS["mode"] == "off" or not relation_slots_ok(sampler, T):
+        missing = "no relation slots (REL_SLOTS off, or a type pair with several relations)"
+    else:
+        return None
+    return ("bf16 input tables are read by the sampler's sums launch only (pre_sums), which "
+            f"does not apply: {missing}")
 
 
 def fused_residual_unsupported(model, sampler):
@@ -797,6 +839,9 @@ class FusedStep:
         nl = len(model.convs)
         if len(sampler.sizes_k) != nl:
             raise ValueError(f"{nl} layers need {nl} sampler hops, got {len(sampler.sizes_k)}")
+        why = fused_bf16_unsupported(model, sampler, x_dict)
+        if why is not None:
+            raise ValueError(f"regnn_nsm_step does not cover these inputs: {why}")
         keys = sorted(x_dict)
         T, K = len(keys), int(x_dict[0].shape[1])
         C = int(model.out_lin.weight.shape[0])
@@ -900,11 +945,15 @@ class FusedStep:
                 max(sampler.sizes_k) <= 63):
             self._tables = (ctypes.c_void_p * T)(*[x_dict[k].data_ptr() for k in keys])
             sampler.typed_sums[nl - 1] = dict(
-                tables=self._tables, T=T, K=K, s_agg=self._buf(W.s_agg), s_w=self._buf(W.s_w),
+                tables=self._tables, dtype=L.dtype_code(x_dict[keys[0]]), T=T, K=K, s_agg=self._buf(W.s_agg), s_w=self._buf(W.s_w),
                 u_self=self._buf(W.u_self), u_rel=self._buf(W.u_rel),
                 # agg0 and bwd0 then read s_agg / s_w / u_self / u_rel only: not the hop's meta
                 layout=sampler_type_layout(sampler, T), meta_unread=True)
             W.pre_sums = 1
+        elif x_dict[keys[0]].dtype != torch.float32:
+            # (fused_bf16_unsupported names the same conditions: agg0 reads fp32 rows only)
+            raise ValueError("regnn_nsm_step: bf16 input tables need the sampler's input sums "
+                             "(pre_sums), which did not come on")
 
     def defer_csc(self):
         """hop 0's transposed index finished by this step's head launch instead of the sampler's
@@ -1175,6 +1224,17 @@ class NSTrainer:
             # a residual model whose hop-0 block exceeds the two-layer form: "auto" takes the
             # module path for every slot, "fused" gets FusedStep's error (below)
             why = fused_residual_unsupported(model, self.slots[0])
+        # bf16 input tables (all of them, or none): read by the sampler's sums launch alone
+        self._bf16 = any(torch.is_tensor(x) and x.dtype == torch.bfloat16
+                         for x in x_dict.values())
+        if why is None and self._bf16:
+            why = fused_bf16_unsupported(model, self.slots[0], x_dict)
+        if self._bf16 and (engine == "module" or why is not None):
+            # (before any buffer is built) the module path reads bf16 tables only through the
+            # sampler's input sums (_module_pre_sums)
+            bad = self._module_bf16_unsupported(self.slots[0])
+            if bad is not None and engine != "fused":
+                raise ValueError(f"bf16 input tables: {bad}")
         early = []
         if engine != "module" and why is None and len(model.convs) == 2:
             ids = {id(p) for p in self.params}
@@ -1224,6 +1284,10 @@ class NSTrainer:
                              getattr(model, "typed_first_layer_ok", lambda _x: False)(x_dict))
         if self.fused is None and self._blocks_ok:
             self._setup_module_slot(self.slots[0])
+        if self._bf16 and self.fused is None and \
+                getattr(self.slots[0].blocks[-1], "pre_sums", None) is None:
+            raise ValueError("bf16 input tables: the module path's input sums (_module_pre_sums) "
+                             "did not come on")
         # REGNN_NS_PIPELINE=0: no second stream (a profiling aid: every kernel's time alone)
         pipeline = pipeline and os.environ.get("REGNN_NS_PIPELINE", "1") != "0"
         self.pipelined = bool(pipeline) and (self.fused is not None or
@@ -1319,6 +1383,35 @@ class NSTrainer:
                 s.hop_strided[0] = True
                 b0.strided_rows = (s.hop_bufs[0]["scnt"], s.sizes_k[0] + 1)
 
+    def _module_bf16_unsupported(self, s):
+        """why the module path cannot train on this trainer's bf16 input tables (None: it can):
+        layer 0 must read the sampler's per-type input sums (_module_pre_sums) and nothing else
+        may read the raw rows."""
+        m = self.model
+        if getattr(m, "feats_type", 3) == 2:
+            return "feats_type 2 (tables that learn) takes fp32 tables only"
+        if not self._blocks_ok:
+            return "the model does not run on device blocks (regcn, self_loop_type 2)"
+        if any(bool(getattr(c, "residual", False)) for c in m.convs):
+            return ("the module path's residual convs project the raw rows (group_input), which "
+                    "reads fp32 tables")
+        if MODULE_LEAN_HOP["mode"] == "off" or MODULE_PRE_SUMS["mode"] == "off":
+            return "MODULE_LEAN_HOP / MODULE_PRE_SUMS is off"
+        tabs = getattr(m, "_type_tables", lambda _x: None)(self.x_dict)
+        if not tabs or any(t is None for t in tabs):
+            return "x_dict keys must be the node types 0..T-1"
+        if any(t.dtype != torch.bfloat16 for t in tabs):
+            return "the tables must share one dtype"
+        if len(tabs) > 4 or any(t.dim() != 2 or t.shape[1] != 128 for t in tabs):
+            return "bf16 tables need width K = 128 and <= 4 node types"
+        if not getattr(m, "typed_first_layer_ok", lambda _x: False)(self.x_dict):
+            return "the typed first layer does not apply (contiguous 16-byte aligned device tables)"
+        if max(s.sizes_k) > 63:
+            return "a fan-out above 63"
+        if not relation_slots_ok(s, len(tabs)):
+            return "no relation slots (a type pair with several relations)"
+        return None
+
     def _module_pre_sums(self, s, last):
         """relation slots, 128-wide inputs, <= 4 node types: the module path's outer hop runs as
         the sampler's sums launch (regnn_ns_hop_typed_sums, strided, on the sampler's stream) and
@@ -1336,7 +1429,10 @@ class NSTrainer:
         U, cnt, xself = z(cap, T, K), z(cap, T), z(cap, K)
         urel = torch.full((cap, T + 1), -1, dtype=torch.int32, device=dev)
         ptrs = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tabs])
-        s.typed_sums[last] = dict(tables=ptrs, T=T, K=K, s_agg=U, s_w=cnt, u_self=xself,
+        if len({t.dtype for t in tabs}) != 1:
+            return
+        s.typed_sums[last] = dict(tables=ptrs, dtype=L.dtype_code(tabs[0]), T=T, K=K, s_agg=U,
+                                  s_w=cnt, u_self=xself,
                                   u_rel=urel, keep=tabs,
                                   # ops.ns_slot_agg and its backward read U / cnt / xself / urel
                                   # (and the block's inv) only: not the hop's per-slot meta

@@ -832,14 +832,22 @@ def ns_typed_agg(blk, tab, n_id, tables, node_type, local_idx, ext=False):
     return _NsTypedAgg.apply(tab, blk, n_id, tables, node_type, local_idx, bool(ext))
 
 
-def ns_typed_agg_ok(tables):
+def ns_typed_agg_ok(tables, pre_sums=False):
     """regnn_ns_typed_agg's operand contract: 1..8 fp32 contiguous device tables of one width
-    64 or 128."""
+    64 or 128. pre_sums: layer 0 reads the sampler's per-type input sums (ns_slot_agg over
+    blk.pre_sums), never the tables, which may then also all be bf16 at the sums launch's shapes
+    (regnn_ns_hop_typed_sums_dt: width 128, <= 4 tables)."""
     if not tables or len(tables) > 8 or any(t is None for t in tables):
         return False
     K = tables[0].shape[1] if tables[0].dim() == 2 else -1
+    dt = tables[0].dtype
+    if dt == torch.bfloat16:
+        if not pre_sums or K != 128 or len(tables) > 4:
+            return False
+    elif dt != torch.float32:
+        return False
     return K in (64, 128) and all(
-        t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == K and
+        t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[1] == K and
         t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tables)
 
 
