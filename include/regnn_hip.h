@@ -289,7 +289,7 @@ int regnn_gat_softmax_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t*
 /* GAT attention, backward (edge_softmax VJP + LeakyReLU + u_add_v), per destination v (CSR):
  *   gz = a * (ga - sum_v a*ga);  gs = gz * (s > 0 ? 1 : slope)
  *   gs_out[e,h] = gs (CSR order); ger[v,h] = sum_v gs;  slab: per (rel, h) sums of gs
- * (d loss / d ee_table) when slab != NULL (requires n_rel*H <= 256). */
+ * (d loss / d ee_table) when slab != NULL (requires n_rel <= 64; any H <= 256). */
 int regnn_gat_softmax_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
                           const float* ee_table, const float* el, const float* er,
                           const float* a, const float* ga, int64_t n_seg, int32_t H, float slope,

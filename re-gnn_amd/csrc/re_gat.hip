@@ -45,6 +45,16 @@ gat_softmax_fwd_generic(const int32_t* __restrict__ ptr, const int32_t* __restri
     }
 }
 
+// Working threads per block of gat_softmax_bwd_generic: the largest multiple of H <= kBlock
+// (H > kBlock: every thread, and no relation bins). Kernel and launch share this one definition:
+// the bins of head h are summed over the columns h, h + H, ... below it.
+__host__ __device__ inline int gat_generic_act(int H) {
+    return H <= kBlock ? kBlock - kBlock % H : kBlock;
+}
+
+// Only the first gat_generic_act(H) threads of a block take work and the grid strides by that
+// count, so a thread's head is tid % H for every H <= kBlock (the grid is sized for that many
+// threads a block).
 __global__ void __launch_bounds__(kBlock)
 gat_softmax_bwd_generic(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
                        const uint8_t* __restrict__ rel, const float* __restrict__ ee,
@@ -54,10 +64,11 @@ gat_softmax_bwd_generic(const int32_t* __restrict__ ptr, const int32_t* __restri
                        float* __restrict__ slab, int n_rel) {
     extern __shared__ float bins[];   // [n_rel][kBlock]; a thread only touches its own column
     const int tid = threadIdx.x;
+    const int act = gat_generic_act(H);
     if (slab) for (int r = 0; r < n_rel; ++r) bins[r * kBlock + tid] = 0.f;
     const int64_t total = n_seg * H;
-    for (int64_t t = (int64_t)blockIdx.x * kBlock + tid; t < total;
-         t += (int64_t)gridDim.x * kBlock) {
+    for (int64_t t = (int64_t)blockIdx.x * act + tid; tid < act && t < total;
+         t += (int64_t)gridDim.x * act) {
         const int64_t v = t / H;
         const int h = int(t - v * H);
         const int b = ptr[v], e = ptr[v + 1];
@@ -78,12 +89,12 @@ gat_softmax_bwd_generic(const int32_t* __restrict__ ptr, const int32_t* __restri
         ger[t] = gsum;
     }
     if (slab) {
-        // kBlock % H == 0, so thread tid always works on head tid % H
+        // act % H == 0 and the stride is a multiple of act: thread tid < act works on head tid % H
         __syncthreads();
         for (int c = tid; c < n_rel * H; c += kBlock) {
             const int r = c / H, h = c - r * H;
             float s = 0.f;
-            for (int t2 = h; t2 < kBlock; t2 += H) s += bins[r * kBlock + t2];
+            for (int t2 = h; t2 < act; t2 += H) s += bins[r * kBlock + t2];
             slab[(int64_t)blockIdx.x * n_rel * H + c] = s;
         }
     }
@@ -962,12 +973,14 @@ int regnn_gat_softmax_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t*
     if (!ptr || !idx || !el || !er || !a || !ga || !gs_out || !ger || H <= 0 || n_seg < 0)
         return REGNN_EINVAL;
     if ((ee_table || slab) && !rel) return REGNN_EINVAL;
-    if (slab && (n_rel <= 0 || n_rel > 64 || kBlock % H)) return REGNN_EUNSUPPORTED;
+    if (slab && (n_rel <= 0 || n_rel > 64)) return REGNN_EUNSUPPORTED;
     if (n_seg == 0) return REGNN_OK;
     const size_t lds = slab ? size_t(n_rel) * kBlock * sizeof(float) : 0;
     const int lg = gat_log2(H);
     if (lg < 0) {
-        hipLaunchKernelGGL(gat_softmax_bwd_generic, dim3(grid_for(n_seg * H, kBlock)),
+        if (slab && H > kBlock) return REGNN_EUNSUPPORTED;
+        const int act = gat_generic_act(H);
+        hipLaunchKernelGGL(gat_softmax_bwd_generic, dim3(grid_for(n_seg * H, act)),
                            dim3(kBlock), lds, stream, ptr, idx, rel, ee_table, el, er, a, ga,
                            n_seg, H, slope, gs_out, ger, slab, n_rel);
         REGNN_LAUNCH_CHECK();

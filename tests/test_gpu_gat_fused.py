@@ -3,10 +3,14 @@ pass, layer/REGATConv.py:80-92) and its backward (attention re-formed from the l
 against the unfused HIP path (gat_attention + head_spmm, pinned on the golden REGATConv vectors)
 on a power-law graph with hub rows, H=8 D=64 and H=4 D=16, with and without the relation bias.
 fp32 at 1e-5 (relative to each tensor's max); the layer-level golden tests in test_gpu_layers.py
-run REGATConv in eval mode, i.e. through the fused path."""
+run REGATConv in eval mode, i.e. through the fused path. The generic head counts (no power of
+two <= 32: the unfused path) run on the ladder graph under the per-element metric of
+_attention_ref.py."""
 import numpy as np
 import pytest
 import torch
+
+import _attention_ref as AR
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -75,19 +79,7 @@ def _hub_graph(N=4000, E=120000, R=7, seed=3):
 
 def _gat_reference(rg, rel_csr, el, er, tab, ft, slope):
     """fp64 torch restatement of layer/REGATConv.py:80-92 over the CSR edge list."""
-    ptr = rg.csr_ptr.long()
-    src = rg.csr_idx.long()
-    dst = torch.repeat_interleave(torch.arange(rg.n_dst, device=DEV), ptr[1:] - ptr[:-1])
-    s = el[src] + er[dst] + (tab[rel_csr.long()] if tab is not None else 0.0)
-    s = torch.nn.functional.leaky_relu(s, slope)
-    H = s.shape[1]
-    m = torch.full((rg.n_dst, H), -torch.inf, dtype=s.dtype, device=DEV)
-    m = m.scatter_reduce(0, dst[:, None].expand(-1, H), s, reduce="amax", include_self=True)
-    ex = torch.exp(s - m[dst])
-    den = torch.zeros(rg.n_dst, H, dtype=s.dtype, device=DEV).index_add(0, dst, ex)
-    a = ex / den[dst]
-    out = torch.zeros(rg.n_dst, H, ft.shape[2], dtype=s.dtype, device=DEV)
-    return out.index_add(0, dst, a[:, :, None] * ft[src])
+    return AR.gat_reference(rg.csr_ptr, rg.csr_idx, rel_csr, el, er, tab, ft, slope)
 
 
 @pytest.mark.parametrize("fused", [True, False])
@@ -170,26 +162,8 @@ def test_attn_dots_vec_order_matches_fp64():
 def _gatv2_reference(rg, rel_csr, fs, fd, att, tab, ft, slope, global_max=False):
     """fp64 torch restatement of layer/REGATv2Conv.py:139-163 (GATv2 score, relation bias,
     per-destination softmax; global_max: mag/utils.py:45-57) and the per-head aggregation."""
-    ptr = rg.csr_ptr.long()
-    src = rg.csr_idx.long()
-    dst = torch.repeat_interleave(torch.arange(rg.n_dst, device=DEV), ptr[1:] - ptr[:-1])
-    e = torch.nn.functional.leaky_relu(fs[src] + fd[dst], slope)             # [E, H, D]
-    s = (e * att).sum(-1)
-    if tab is not None:
-        s = s + tab[rel_csr.long()]
-    H = s.shape[1]
-    if global_max:
-        ex = torch.exp(s - s.max())
-        den = torch.zeros(rg.n_dst, H, dtype=s.dtype, device=DEV).index_add(0, dst, ex)
-        a = ex / (den[dst] + 1e-16)
-    else:
-        m = torch.full((rg.n_dst, H), -torch.inf, dtype=s.dtype, device=DEV)
-        m = m.scatter_reduce(0, dst[:, None].expand(-1, H), s, reduce="amax", include_self=True)
-        ex = torch.exp(s - m[dst])
-        den = torch.zeros(rg.n_dst, H, dtype=s.dtype, device=DEV).index_add(0, dst, ex)
-        a = ex / den[dst]
-    out = torch.zeros(rg.n_dst, H, ft.shape[2], dtype=s.dtype, device=DEV)
-    return out.index_add(0, dst, a[:, :, None] * ft[src])
+    return AR.gatv2_reference(rg.csr_ptr, rg.csr_idx, rel_csr, fs, fd, att, tab, ft, slope,
+                             global_max)
 
 
 @pytest.mark.parametrize("global_max", [False, True])
@@ -295,3 +269,55 @@ def test_attention_single_chunk_long_rows_vs_fp64(kind):
     for i, (x, w) in enumerate(zip(got, want)):
         err = (x.double() - w).abs().max().item() / _rel(w)
         assert err <= 1e-5, f"{kind} output {i}: rel err {err:.3e}"
+
+
+@pytest.mark.parametrize("H,D,N,recipe,fused", [
+    (3, 4, 320, "unit", True), (5, 8, 320, "unit", False), (6, 8, 320, "unit", False),
+    (12, 16, 320, "unit", True), (64, 4, 320, "unit", False), (3, 4, 320, "wide", False),
+    (12, 4, 45000, "unit", False)])
+def test_gat_generic_heads_relation_table_vs_fp64(H, D, N, recipe, fused):
+    """head counts that are no power of two <= 32 with a relation table that needs its gradient:
+    the thread-per-(destination, head) softmax kernels, whose backward bins the table's gradient
+    per thread column (the first 256 - 256 % H threads of a block take work, so a thread keeps
+    the head tid % H whatever H is; H = 5 leaves one thread idle, H = 12 four, H = 64 none).
+    ops.gat_fused takes the unfused path for such H. On the ladder graph (_attention_ref:
+    in-degrees 0 .. 300, no self loops, so destinations without in-edges occur) in its three plan
+    forms, which the per-head SpMM and its backward take. `wide`: exact-grid logits over
+    [-4, 16]. The last case has more (destination, head) pairs than the capped grid has working
+    threads, so the grid-stride loop runs: the stride must keep a thread's head too.
+    Forward and every gradient against the fp64 restatement: max |got - ref| / (scale + 2^-100)
+    <= 1e-5 elementwise, scale = the same reduction over absolute values, so an error in a short
+    row is not hidden under the hub rows. An fp32 emulation of these kernels' summation order
+    stays below 1.1e-6 under this metric on every case."""
+    from regnn_hip import ops
+    if N > 320:
+        assert N * H > 2048 * (256 - 256 % H)      # kMaxGrid blocks of working threads
+    ft0, el0, er0, tab0, gy, slope = (t.to(DEV) if torch.is_tensor(t) else t for t in
+                                      AR.gat_inputs(recipe, N, H, D, AR.N_REL, 1000 * H + D))
+    want = scale = None
+    failures = []
+    for form in AR.PLAN_FORMS:
+        rg, e_feat = AR.ladder_graph(form, DEV, N)
+        pack = rg.rel_pack(e_feat, num_rel=AR.N_REL)
+        if want is None:                               # the CSR is the same in every form
+            want, scale = AR.gat_case_ref(rg.csr_ptr, rg.csr_idx, pack.rel_csr, el0, er0, tab0,
+                                          ft0, gy, slope)
+        # NaN-filled blocks of the outputs' sizes go back to the allocator: a skipped store is
+        # likely to surface as NaN instead of a stale correct row
+        junk = [torch.full(sh, float("nan"), device=DEV) for sh in
+                [(N, H, D)] * 2 + [(rg.E, H)] * 3 + [(N, H)] * 2]
+        del junk
+        ft, el, er, tab = (t.clone().requires_grad_(True) for t in (ft0, el0, er0, tab0))
+        if fused:
+            y = ops.gat_fused(rg, el, er, ft, tab, pack, slope)
+        else:
+            y = ops.head_spmm(rg, ops.gat_attention(rg, el, er, tab, pack, slope), ft)
+        y.backward(gy)
+        got = {"out": y.detach(), "g_ft": ft.grad, "g_el": el.grad, "g_er": er.grad,
+               "g_tab": tab.grad}
+        for name in sorted(want):
+            err = AR.rel_err(got[name], want[name], scale[name])
+            print(f"H={H} D={D} N={N} {recipe} {form} {name}: {err:.3e}")
+            if not err <= AR.TOL_F32:
+                failures.append(f"{form} {name}: err {err:.3e}")
+    assert not failures, "; ".join(failures)
