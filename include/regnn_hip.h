@@ -41,7 +41,10 @@ enum { REGNN_F32 = 0, REGNN_BF16 = 1 };
  * <rows, gx_raw> / out_scale (out_scale > 0). Not combinable with edge_grad or the _next call. */
 enum { REGNN_SELF_PRESCALED = 0x100 };
 
-/* ABI version (bumped on any signature or semantics change; currently 50). */
+/* ABI version (bumped on any signature or semantics change; currently 51).
+ * ABI 51 removed the transposed index's one-launch build, whose workgroups waited on the last one
+ * (regnn_ns_hop strided = 3 and a NULL csc_rank on a strided hop, regnn_ns_csc_job's kind and
+ * whole-index members): the two-launch build without a wait is the only one. */
 int regnn_abi_version(void);
 
 /* Tuning knob (process-wide, for A/B measurements; defaults are the shipped configuration).
@@ -550,7 +553,7 @@ int regnn_sample_fill(const int32_t* ptr, const int32_t* idx, const int32_t* tar
  *  g2l, first  uint64 [num_nodes] dedup tables: g2l zero-filled, first all-ones, once.
  *  Per-hop scratch (cap_dst = capacity of the hop's targets, k = fan-out, cap_e = cap_dst*(k+1)):
  *  samp, spos [cap_dst*k] int32; scnt [cap_dst] int32; gsrc [cap_e] int32; flag [cap_e] uint8;
- *  tiles [ceil(cap_e/1024) + 4] int32, zero-filled once; status [ceil(cap_dst/1024)] uint64
+ *  tiles [ceil(cap_e/1024) + 1] int32, zero-filled once; status [ceil(cap_dst/1024)] uint64
  *  (row-offset look-back, zero-filled once).
  *  Block output (mag/regnn_layers.py:90-99 with self_loop_type 2): blk_ptr [cap_dst+1],
  *  blk_idx [cap_e] (local source ids; row i's self loop last), blk_rel [cap_e] uint8 (edge type
@@ -632,29 +635,25 @@ int regnn_ns_batch(const int64_t* perm, int64_t n_perm, int32_t batch, int32_t r
  * [i S, i S + cnt_i) (S = k + 1, cnt_i = scnt[i], sampled positions ascending), its self loop at
  * i S + cnt_i, the other slots empty (blk_idx -1); blk_ptr is not written. Sampling and
  * placement run as one launch (no row-offset scan), the de-duplication as one pass (decoupled
- * look-back over status), the transposed index by many blocks in one launch (the last block
- * to resolve scans the counts and publishes csc_ptr, then every block places its entries):
- * 3 launches with de-duplication and the transposed index, 1 meta-only. Strided buffer sizes:
- * tiles >= ceil(cap_e / 1024) + 4 ints (the CSR path's tile words, then the index's own arrival
- * ticket, published stamp and sticky error word at tiles[ceil(cap_e / 1024) + 3]: 1 when a block
- * gave up waiting for the publish and placed nothing -- the caller checks it), status >=
- * ceil(cap_e / 1024) int64 (ABI 43). sizes[8 + hop] must be zero on entry (regnn_ns_batch zeroes sizes[8 ..]);
- * the hop adds its edges to it and to state[5]. strided = 2 (with the transposed index, no
- * edge meta): everything but the transposed index and the sampled edges' blk_idx, which a
- * second call with strided = 3 and the same arguments then writes (on another stream if the
- * caller wants: nothing the next hop reads depends on it).
- * csc_rank (ABI 48; may be NULL: the single launch above) [cap_e] int32, strided = 1 with the
- * transposed index and no edge meta: the index in two launches, neither with a wait between
- * workgroups -- the first resolves every slot's local source id, counts the sources' entries
- * (csc_cnt) and stores each slot's rank in its source's segment (csc_rank); the second's
- * workgroups (1024 slots each) all scan the counts by themselves and place their own slots at
- * prefix[source] + rank, workgroup 0 also writing csc_ptr, the hub list and the piece table (the
- * same values and layout; the error word is never raised). strided = 4 (needs csc_rank): the
- * first of the two only -- csc_cnt / csc_rank / blk_idx final, csc_ptr / csc_ent / csc_long
- * not written; regnn_nsm_step with csc_pending = 1 finishes the index beside its head.
- * strided = 5 (ABI 50; needs csc_rank, the transposed index, no edge meta): the second of the two
- * only (scan + placement, one launch) -- for a hop whose call ran with strided = 2 and whose
- * counts and ranks a later regnn_ns_hop_typed_sums launch wrote (regnn_ns_csc_job kind 1). */
+ * look-back over status), the transposed index in two launches, neither with a wait between
+ * workgroups: 4 launches with de-duplication and the transposed index, 1 meta-only. Strided
+ * buffer sizes: status >= ceil(cap_e / 1024) int64 (ABI 43); tiles is not touched.
+ * sizes[8 + hop] must be zero on entry (regnn_ns_batch zeroes sizes[8 ..]); the hop adds its edges
+ * to it and to state[5].
+ * csc_rank [cap_e] int32 (ABI 48): needed by a strided hop with the transposed index and no edge
+ * meta (REGNN_EINVAL without it, before any launch; ignored by the CSR layout and with edge meta,
+ * where one workgroup builds the index). The index's first launch resolves every slot's local
+ * source id, counts the sources' entries (csc_cnt) and stores each slot's rank in its source's
+ * segment (csc_rank); the second's workgroups (1024 slots each) all scan the counts by themselves
+ * and place their own slots at prefix[source] + rank, workgroup 0 also writing csc_ptr, the hub
+ * list and the piece table. The modes of a hop with the transposed index and no edge meta:
+ * strided = 1: both launches. strided = 4: the first only -- csc_cnt / csc_rank / blk_idx final,
+ * csc_ptr / csc_ent / csc_long not written; regnn_nsm_step with csc_pending = 1 finishes the
+ * index beside its head. strided = 2: neither, and the sampled edges' blk_idx not written -- a
+ * later regnn_ns_hop_typed_sums launch writes the counts and ranks (its csc job; nothing the next
+ * hop reads depends on them), then strided = 5 (ABI 50; needs csc_rank, the transposed index, no
+ * edge meta; no sampling): the second launch only, or again regnn_nsm_step with csc_pending = 1.
+ * Any other hop takes strided = 0 (the CSR layout) or 1; strided = 3 is REGNN_EINVAL (ABI 51). */
 #define REGNN_CSC_PIECE 1024
 #define REGNN_CSC_LONG_CAP (32768 / 17 + 1)          /* hub rows of a <= 32768-edge block */
 #define REGNN_CSC_LONG_NPIECE (REGNN_CSC_LONG_CAP + 1)
@@ -684,31 +683,21 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
  * regnn_nsm_step with pre_sums = 1; they depend on the batch only, so the sampler computes them
  * ahead of the model). T = n_types in [1, 4], k <= 63, tables / s_agg / u_self 16-byte aligned.
  * One launch. The summation order is fixed (the result is a function of the batch).
- * csc (may be NULL; ABI 42): an earlier hop's transposed index, whose regnn_ns_hop call ran with
- * strided = 2 (de-duplication done, index left out), built by extra workgroups of the same launch
- * (regnn_ns_hop strided = 3's work, beside the sums instead of before them; same state / sizes).
- * kind (ABI 50) REGNN_NS_CSC_JOB_RANK: the leading ceil(cap_e / 256) workgroups write only the
- * split build's first half (regnn_ns_hop strided = 4's counts, ranks and local source ids: no
- * wait between workgroups, tiles / csc_ptr / csc_ent / csc_long not touched) and return; a
- * regnn_ns_hop call with strided = 5, or regnn_nsm_step with csc_pending = 1, finishes the index.
- * Needs csc_rank (REGNN_EINVAL without it). */
-#define REGNN_NS_CSC_JOB_BUILD 0   /* the whole index (waits for the last workgroup's scan) */
-#define REGNN_NS_CSC_JOB_RANK 1    /* counts + ranks only */
+ * csc (may be NULL; ABI 42, the rank job alone since ABI 51): an earlier hop whose regnn_ns_hop
+ * call ran with strided = 2 (de-duplication done, index left out). The leading ceil(cap_e / 256)
+ * workgroups of the launch write the index's first half (regnn_ns_hop strided = 4's counts, ranks
+ * and local source ids: no wait between workgroups, csc_ptr / csc_ent / csc_long not touched)
+ * beside the sums instead of before them, and return; a regnn_ns_hop call with strided = 5, or
+ * regnn_nsm_step with csc_pending = 1, finishes the index. REGNN_EINVAL: a NULL member, hop not
+ * earlier than this call's, cap_e <= 0; REGNN_EUNSUPPORTED: cap_e > 32768. */
 typedef struct regnn_ns_csc_job {
     int32_t hop;                /* that hop */
     int32_t cap_e;              /* its block's slots: cap_dst * (k + 1) <= 32768 */
     const int32_t* gsrc;        /* its buffers, as passed to regnn_ns_hop */
     const uint64_t* g2l;
     int32_t* blk_idx;
-    const int32_t* blk_row;
-    const uint8_t* blk_rel;
     int32_t* csc_cnt;
-    int32_t* tiles;             /* >= ceil(cap_e / 1024) + 4 ints (as regnn_ns_hop) */
-    int32_t* csc_ptr;
-    int32_t* csc_ent;
-    int32_t* csc_long;
-    int32_t* csc_rank;          /* ABI 50: [cap_e], kind REGNN_NS_CSC_JOB_RANK (else may be NULL) */
-    int32_t kind;               /* ABI 50: REGNN_NS_CSC_JOB_* */
+    int32_t* csc_rank;          /* [cap_e] */
 } regnn_ns_csc_job;
 /* layout (may be NULL; ABI 47): node ids grouped by type -- type t's nodes are the ids
  * [type_off[t], type_off[t + 1]) (equal offsets: a type without nodes), node u's table row is

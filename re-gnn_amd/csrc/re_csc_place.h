@@ -3,8 +3,8 @@
 // ns_csc_rank_kernel wrote them in an earlier launch -- a workgroup needs nothing from any other:
 // each one loads all the counts, forms their exclusive prefix in LDS by itself and places its own
 // 1024 slots at prefix[source] + rank. Workgroup 0 also writes csc_ptr, the hub list and the
-// piece table, the values and layout csc_scan_block (re_ns.hip) writes. No ticket, no flag, no
-// spin: the only ordering is the launch boundary before it. Runs as its own launch
+// piece table, the values and layout ns_csc_kernel (re_ns.hip) writes. No ticket, no flag, no
+// wait: the only ordering is the launch boundary before it. Runs as its own launch
 // (ns_csc_place_kernel, re_ns.hip) or as extra workgroups of the two-layer step's head launch
 // (re_nsm2.hip), whose next launch (the gather) is the index's first reader.
 #pragma once

@@ -686,222 +686,18 @@ ns_csc_kernel(const int32_t* __restrict__ sizes, int hop, const int32_t* __restr
     }
 }
 
-// The transposed index built by many blocks in one launch (replaces the one-workgroup
-// ns_csc_kernel on the strided path). Every block resolves its slots' local source ids (as
-// ns_resolve_kernel) and takes each entry's rank in its source's segment from the counter's
-// returned atomic; the last block to arrive (a ticket) scans the counts into csc_ptr, the hub list
-// and the piece table and publishes them (agent release, a stamped flag); every block then places
-// its own entries at csc_ptr[source] + rank (the others wait on the flag: the last block is
-// running, it took the last ticket). The order inside a segment follows the counters' atomics
-// (unspecified: the consumer's sums are exact fixed-point).
-constexpr int kCscScanT = 256;             // 256-thread blocks: they fit beside the model's kernels
-// counts per lane per pass (lane-contiguous): 16 in the index's own launch, 4 beside the sums
-// (whose launch would otherwise hold the larger LDS in every block)
-template <int Q>
-constexpr int csc_scan_pad() { return 64 * Q + 64; }   // LDS words per wave (padded)
-
-// The scan of the per-source counts by one 256-thread block: per pass each wave loads 64 Q
-// counts coalesced, transposes them through LDS (index e at e + e / Q) so each lane holds Q
-// consecutive counts, scans lane-serially and across the wave (shuffles),
-// combines the four waves through LDS, and writes csc_ptr back coalesced through the same LDS.
-// Hub rows (more than kCscShort entries) are listed ascending with their pieces.
-template <int Q>
-__device__ void csc_scan_block(const int32_t* __restrict__ csc_cnt, int n,
-                               int32_t* __restrict__ csc_ptr, int32_t* __restrict__ csc_long,
-                               int* __restrict__ sbuf, int* __restrict__ swave) {
-    constexpr int NW = kCscScanT / 64, WE = 64 * Q;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int* buf = sbuf + w * csc_scan_pad<Q>();
-    int carry = 0, lcarry = 0, pcarry = 0;
-    int4* pieces = reinterpret_cast<int4*>(csc_long + REGNN_CSC_LONG_TAB);
-    for (int base = 0; base < n; base += NW * WE) {
-        const int wb = base + w * WE;
-        int v[Q];
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const int e = j * 64 + lane;
-            v[j] = wb + e < n ? csc_cnt[wb + e] : 0;   // (behind the ticket's acquire)
-        }
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const int e = j * 64 + lane;
-            buf[e + e / Q] = v[j];
-        }
-        __syncthreads();
-        int s = 0, nl = 0, np = 0;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            v[q] = buf[lane * (Q + 1) + q];
-            s += v[q];
-            nl += v[q] > kCscShort ? 1 : 0;
-            np += v[q] > kCscShort ? (v[q] + kCscPiece - 1) / kCscPiece : 0;
-        }
-        int xs = s, xl = nl, xp = np;             // inclusive wave scans
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int ys = __shfl_up(xs, o, 64), yl = __shfl_up(xl, o, 64),
-                      yp = __shfl_up(xp, o, 64);
-            if (lane >= o) {
-                xs += ys;
-                xl += yl;
-                xp += yp;
-            }
-        }
-        if (lane == 63) {
-            swave[w] = xs;
-            swave[NW + w] = xl;
-            swave[2 * NW + w] = xp;
-        }
-        __syncthreads();
-        int ws = carry, wl = lcarry, wp = pcarry, ts = 0, tl = 0, tp = 0;
-#pragma unroll
-        for (int u = 0; u < NW; ++u) {
-            const int a = swave[u], b = swave[NW + u], c = swave[2 * NW + u];
-            if (u < w) {
-                ws += a;
-                wl += b;
-                wp += c;
-            }
-            ts += a;
-            tl += b;
-            tp += c;
-        }
-        int off = ws + xs - s, loff = wl + xl - nl, poff = wp + xp - np;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int i = wb + lane * Q + q;
-            buf[lane * (Q + 1) + q] = off;
-            if (v[q] > kCscShort && i < n) {
-                const int li = loff++;
-                csc_long[1 + li] = i;
-                const int npc = (v[q] + kCscPiece - 1) / kCscPiece;
-                for (int k = 0; k < npc; ++k, ++poff)
-                    pieces[poff] = make_int4(i, off + k * kCscPiece,
-                                             min(kCscPiece, v[q] - k * kCscPiece),
-                                             (li << 16) | (k << 8) | npc);
-            }
-            off += v[q];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const int e = j * 64 + lane;
-            if (wb + e < n) csc_ptr[wb + e] = buf[e + e / Q];
-        }
-        carry += ts;
-        lcarry += tl;
-        pcarry += tp;
-        __syncthreads();                          // buf / swave reused by the next pass
-    }
-    if (threadIdx.x == 0) {
-        csc_ptr[n] = carry;
-        csc_long[0] = lcarry;
-        csc_long[REGNN_CSC_LONG_NPIECE] = pcarry;
-    }
-}
-
-struct NsCscJob {
-    int hop, cap_e;
-    const int32_t* gsrc; const uint64_t* g2l;
-    int32_t* blk_idx; const int32_t* blk_row; const uint8_t* blk_rel;
-    int32_t* csc_cnt; int32_t* tiles; int32_t* csc_ptr; int32_t* csc_ent; int32_t* csc_long;
-    int32_t* csc_rank; int kind;           // kind REGNN_NS_CSC_JOB_RANK: counts + ranks only
-};
-
-// The strided transposed index's control words, past everything the CSR path's flag tiles use
-// (tiles[0 .. n_tiles]: the tile counts / prefixes and their ticket): ctl[0] the arrival ticket
-// (reset by the last block), ctl[1] the published stamp (no other kernel writes it, so a leftover
-// value never equals this hop's stamp), ctl[2] a sticky error word (1: a waiting block's bounded
-// spin ran out before the publish; its entries were not placed). tiles >= n_tiles + 4 ints.
-__device__ __forceinline__ int32_t* csc_ctl(const NsCscJob& J) {
-    return J.tiles + (J.cap_e + kNsTile - 1) / kNsTile + 1;
-}
-
-// One workgroup (block `bid` of `nb`) of the transposed index's launch (control words: csc_ctl)
-template <int Q>
-__device__ void csc_resolve_place(const NsCscJob& J, const int32_t* __restrict__ sizes,
-                                  const int64_t* __restrict__ state, int bid, int nb) {
-    __shared__ int sbuf[(kCscScanT / 64) * csc_scan_pad<Q>()];
-    __shared__ int swave[3 * (kCscScanT / 64)];
-    __shared__ int last, ok;
-    int32_t* ctl = csc_ctl(J);
-    const int bp = bid * kCscScanT + threadIdx.x;
-    int lid = -1, rank = 0, ent = 0;
-    if (bp < J.cap_e) {
-        const int u = J.gsrc[bp];
-        if (u != -2) {                     // -2: an empty slot of the strided layout
-            ent = (J.blk_row[bp] << 8) | int(J.blk_rel[bp]);
-            if (u < 0) {                   // the self loop
-                lid = J.blk_idx[bp];
-            } else {
-                lid = int32_t(uint32_t(J.g2l[u]));
-                J.blk_idx[bp] = lid;
-            }
-            rank = atomicAdd(J.csc_cnt + lid, 1);        // integer: exact in any order
-        }
-    }
-    const uint32_t stamp = ns_stamp(state, J.hop);
-    __syncthreads();                       // every count of this block added (values returned)
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last = __hip_atomic_fetch_add(ctl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-               nb - 1;
-        ok = 1;
-    }
-    __syncthreads();
-    if (last) {
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        csc_scan_block<Q>(J.csc_cnt, sizes[J.hop + 1], J.csc_ptr, J.csc_long, sbuf, swave);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(ctl, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ctl + 1, int(stamp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    } else if (threadIdx.x == 0) {
-        // one lane polls the published stamp (relaxed), then one acquire; bounded (a watchdog:
-        // the last block holds a CU and runs to the publish). A spin that runs out places
-        // nothing (csc_ptr may be stale) and raises the sticky error word the host checks
-        // (DeviceSampler.check_index)
-        int seen = 0;
-        for (uint32_t spins = 0; spins < (1u << 26) && !seen; ++spins) {
-            seen = uint32_t(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT)) == stamp;
-            if (!seen) __builtin_amdgcn_s_sleep(1);
-        }
-        if (!seen) {
-            __hip_atomic_store(ctl + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = 0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    if (lid >= 0 && ok) J.csc_ent[J.csc_ptr[lid] + rank] = ent;
-}
-
-inline int csc_blocks(int64_t cap_e) { return int((cap_e + kCscScanT - 1) / kCscScanT); }
-
-__global__ void __launch_bounds__(kCscScanT)
-ns_resolve_csc_kernel(NsCscJob J, const int32_t* __restrict__ sizes,
-                      const int64_t* __restrict__ state) {
-    csc_resolve_place<16>(J, sizes, state, blockIdx.x, gridDim.x);
-}
-
-// The same index in two launches, neither with a wait between workgroups (ABI 48). First half:
+// The same index by many workgroups (the strided path without edge meta), in two halves, neither
+// with a wait between workgroups (ABI 48; the only many-workgroup build since ABI 51). First half:
 // every slot's local source id (as ns_resolve_kernel), the source's count and the slot's rank in
 // its source's segment (the counter's returned atomic: unspecified order, exact counts) -- the
 // only part that reads the dedup table the next batch's sampling overwrites. The second half
 // (csc_scan_place, re_csc_place.h) reads the slot's own buffers only.
+struct NsCscJob {                          // the first half as a job of a later hop's sums launch
+    int hop, cap_e;
+    const int32_t* gsrc; const uint64_t* g2l;
+    int32_t* blk_idx; int32_t* csc_cnt; int32_t* csc_rank;
+};
+
 static_assert(kCscPlaceMax == kCscMax && kCscPlaceShort == kCscShort, "re_csc_place.h");
 __device__ __forceinline__ void csc_rank_slot(const int32_t* __restrict__ gsrc,
                                               const uint64_t* __restrict__ g2l,
@@ -952,7 +748,7 @@ struct NsSumArgs {
     int32_t* scnt; uint8_t* blk_rel; float* inv; int32_t* e_type; int64_t* e_off;
     const void* xt[8]; int T;               // the tables' rows: float or bf16_t (the kernel's XT)
     float* s_agg; float* s_w; float* u_self; int32_t* u_rel;
-    NsCscJob csc; int csc_blocks;          // an earlier hop's transposed index (csc_blocks > 0)
+    NsCscJob csc; int csc_blocks;          // an earlier hop's index ranks (csc_blocks > 0)
     // DERIVE (node ids grouped by type, regnn_ns_type_layout): type q's first node id (q = 1..3;
     // INT_MAX past the last type) and, per target type, a byte per source type: the pair's
     // relation (0xFF: none). By value, so a captured graph holds them
@@ -1033,16 +829,13 @@ constexpr int kNsSumWaves = 4;             // waves per block (256 threads: they
 template <int G, int NT, bool DERIVE, typename XT>
 __global__ void __launch_bounds__(64 * kNsSumWaves, kNsSumOcc)
 ns_sample_sums_kernel(NsSumArgs A) {
-    // the first csc_blocks workgroups build the earlier hop's transposed index (latency-bound:
-    // dispatched first, they run beside the sums instead of ahead of them)
-    // kind REGNN_NS_CSC_JOB_RANK: the split build's first half only (ns_csc_rank_kernel's body,
-    // a slot per thread: no wait between workgroups), the placement a launch of its own after
+    // the first csc_blocks workgroups take the earlier hop's transposed index's first half
+    // (latency-bound: dispatched first, they run beside the sums instead of ahead of them):
+    // ns_csc_rank_kernel's body, a slot per thread, no wait between workgroups; the placement
+    // follows in a launch after this one
     if (int(blockIdx.x) < A.csc_blocks) {
-        if (A.csc.kind == REGNN_NS_CSC_JOB_RANK)
-            csc_rank_slot(A.csc.gsrc, A.csc.g2l, A.csc.blk_idx, A.csc.csc_cnt, A.csc.csc_rank,
-                          A.csc.cap_e, blockIdx.x * (64 * kNsSumWaves) + threadIdx.x);
-        else
-            csc_resolve_place<4>(A.csc, A.sizes, A.state, blockIdx.x, A.csc_blocks);
+        csc_rank_slot(A.csc.gsrc, A.csc.g2l, A.csc.blk_idx, A.csc.csc_cnt, A.csc.csc_rank,
+                      A.csc.cap_e, blockIdx.x * (64 * kNsSumWaves) + threadIdx.x);
         return;
     }
     const int bid = blockIdx.x - A.csc_blocks, nbk = gridDim.x - A.csc_blocks;
@@ -1915,25 +1708,17 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
     if (cap_e >= (int64_t(1) << 31)) return REGNN_EUNSUPPORTED;
     const int n_tiles = int((cap_e + kNsTile - 1) / kNsTile);
     if (csc && cap_e > kCscMax) return REGNN_EUNSUPPORTED;
-    // strided = 4: the split index's first half only (the caller's step finishes it)
+    if (strided == 3) return REGNN_EINVAL;     // the one-launch build on its own (gone with ABI 51)
+    // strided = 4: the index's first half only (the caller's step finishes it)
     if (strided == 4 && (!csc || !csc_rank || edge_type || lean)) return REGNN_EINVAL;
+    // a strided hop's index without edge meta is built in two halves through csc_rank (with edge
+    // meta: ns_resolve_kernel + ns_csc_kernel; strided = 2 leaves the index to later calls)
+    if (strided && strided != 2 && csc && !edge_type && !csc_rank) return REGNN_EINVAL;
     if (strided == 5) {
-        // the split index's second half only (counts + ranks: a sums launch's rank job)
+        // the index's second half only (counts + ranks: a sums launch's rank job)
         if (!csc || !csc_rank || edge_type || lean) return REGNN_EINVAL;
         return ns_csc_place_launch(sizes, hop, int(cap_e), k, csc_cnt, csc_rank, blk_idx, blk_rel,
                                    csc_ptr, csc_ent, csc_long, stream);
-    }
-    if (strided == 3) {
-        // the transposed index only (the part a strided = 2 call left out), on whatever stream
-        // the caller runs it: resolve + counts + ranks, scan, placement
-        if (!csc || edge_type || lean) return REGNN_EINVAL;
-        const int ce = int(cap_e);
-        const NsCscJob J{hop, ce, gsrc, g2l, blk_idx, blk_row, blk_rel, csc_cnt, tiles, csc_ptr,
-                         csc_ent, csc_long, nullptr, REGNN_NS_CSC_JOB_BUILD};
-        hipLaunchKernelGGL(ns_resolve_csc_kernel, dim3(unsigned(csc_blocks(cap_e))),
-                           dim3(kCscScanT), 0, stream, J, sizes, state);
-        REGNN_LAUNCH_CHECK();
-        return REGNN_OK;
     }
     if (strided) {
         // sampling + placement in one launch, no row-offset scan (the layout above)
@@ -1958,26 +1743,17 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
         hipLaunchKernelGGL(ns_flags_finish_kernel, dim3(n_tiles), dim3(kBlock), 0, stream, gsrc,
                            sizes, hop, state, g2l, first, status, n_id, ce);
         REGNN_LAUNCH_CHECK();
-        if (csc && !edge_type && strided == 2) return REGNN_OK;   // the index: a strided = 3 call
-        if (csc && !edge_type && csc_rank) {
+        if (csc && !edge_type) {
             // the index in two launches without a wait between workgroups: counts + ranks, then
-            // every workgroup's own scan and placement (strided = 4: left to the caller's step)
+            // every workgroup's own scan and placement (strided = 2: both left to the caller, a
+            // sums launch's rank job and a strided = 5 call or its step; 4: the second half)
+            if (strided == 2) return REGNN_OK;
             hipLaunchKernelGGL(ns_csc_rank_kernel, dim3(unsigned((cap_e + kBlock - 1) / kBlock)),
                                dim3(kBlock), 0, stream, gsrc, g2l, blk_idx, csc_cnt, csc_rank, ce);
             REGNN_LAUNCH_CHECK();
             if (strided == 4) return REGNN_OK;
             return ns_csc_place_launch(sizes, hop, ce, k, csc_cnt, csc_rank, blk_idx, blk_rel,
                                        csc_ptr, csc_ent, csc_long, stream);
-        }
-        if (csc && !edge_type) {
-            // the transposed index by many blocks in one launch: resolve + counts + ranks, the
-            // last block's scan, every block's placement
-            const NsCscJob J{hop, ce, gsrc, g2l, blk_idx, blk_row, blk_rel, csc_cnt, tiles,
-                             csc_ptr, csc_ent, csc_long, nullptr, REGNN_NS_CSC_JOB_BUILD};
-            hipLaunchKernelGGL(ns_resolve_csc_kernel, dim3(unsigned(csc_blocks(cap_e))),
-                               dim3(kCscScanT), 0, stream, J, sizes, state);
-            REGNN_LAUNCH_CHECK();
-            return REGNN_OK;
         }
         hipLaunchKernelGGL(ns_resolve_kernel, dim3(unsigned((cap_e + kBlock - 1) / kBlock)),
                            dim3(kBlock), 0, stream, gsrc, sizes, hop, g2l, blk_idx, ce, ntype,
@@ -2092,20 +1868,14 @@ int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uin
         return REGNN_EINVAL;
     A.s_agg = s_agg; A.s_w = s_w; A.u_self = u_self; A.u_rel = u_rel;
     if (csc) {
-        if (!csc->gsrc || !csc->g2l || !csc->blk_idx || !csc->blk_row || !csc->blk_rel ||
-            !csc->csc_cnt || !csc->tiles || !csc->csc_ptr || !csc->csc_ent || !csc->csc_long ||
+        if (!csc->gsrc || !csc->g2l || !csc->blk_idx || !csc->csc_cnt || !csc->csc_rank ||
             csc->hop < 0 || csc->hop >= hop || csc->cap_e <= 0)
             return REGNN_EINVAL;
-        const bool rank = csc->kind == REGNN_NS_CSC_JOB_RANK;
-        if (!rank && csc->kind != REGNN_NS_CSC_JOB_BUILD) return REGNN_EINVAL;
-        if (rank && !csc->csc_rank) return REGNN_EINVAL;
         if (csc->cap_e > kCscMax) return REGNN_EUNSUPPORTED;
-        A.csc = NsCscJob{csc->hop, csc->cap_e, csc->gsrc, csc->g2l, csc->blk_idx, csc->blk_row,
-                         csc->blk_rel, csc->csc_cnt, csc->tiles, csc->csc_ptr, csc->csc_ent,
-                         csc->csc_long, csc->csc_rank, csc->kind};
-        // the rank job: a slot per thread of the sums launch's 256-thread workgroups
-        A.csc_blocks = rank ? (csc->cap_e + 64 * kNsSumWaves - 1) / (64 * kNsSumWaves)
-                            : csc_blocks(csc->cap_e);
+        A.csc = NsCscJob{csc->hop, csc->cap_e, csc->gsrc, csc->g2l, csc->blk_idx, csc->csc_cnt,
+                         csc->csc_rank};
+        // a slot per thread of the sums launch's 256-thread workgroups
+        A.csc_blocks = (csc->cap_e + 64 * kNsSumWaves - 1) / (64 * kNsSumWaves);
     }
     // REGNN_NS_SUM_BLOCKS: N > 0 caps the grid at N blocks, < 0: a block per row group whatever
     // their number; 0 / unset: no more blocks than the GPU holds at once, each taking the same

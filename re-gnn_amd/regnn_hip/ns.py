@@ -14,7 +14,9 @@ synchronisation, so one training step is one HIP-graph replay.
 
 The sampled indices follow the build's sampler spec (oracle/sampler_oracle.py, bit-exact).
 """
+import contextlib
 import ctypes
+import gc
 import os
 
 import torch
@@ -122,11 +124,10 @@ class DeviceSampler:
             ce = cd * (k + 1)
             nt = (ce + 1023) // 1024
             z = lambda n, dt=torch.int32: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
-            # tiles: the CSR de-duplication's nt tile counts and their ticket, then the strided
-            # transposed index's own ticket, published stamp and error word (nt + 4); status:
+            # tiles: the CSR de-duplication's nt tile counts and their ticket (nt + 1); status:
             # the strided de-duplication's look-back too (>= ceil(ce / 1024) tiles)
             self.hop_bufs.append(dict(samp=z(cd * k), spos=z(cd * k), scnt=z(cd), gsrc=z(ce),
-                                      flag=z(ce, torch.uint8), tiles=z(nt + 4),
+                                      flag=z(ce, torch.uint8), tiles=z(nt + 1),
                                       status=z(max((cd + 1023) // 1024, nt), torch.int64)))
             blk = NSBlock(z(cd + 1), z(ce), z(ce, torch.uint8), z(ce),
                           torch.ones(cd, dtype=torch.float32, device=dev), cd, caps[h + 1], ce, dev,
@@ -138,7 +139,7 @@ class DeviceSampler:
         # sums_fresh[h]: the latest run_hops wrote hop h's layer-0 input sums (typed_sums path)
         self.sums_fresh = [False] * len(self.sizes_k)
         self.csc = [None] * len(self.sizes_k)      # per hop: (cnt, ptr, ent, long) or None
-        # the split index build (CSC_SPLIT): per hop each slot's rank in its source's segment
+        # per hop with an index: each slot's rank in its source's segment (regnn_ns_hop csc_rank)
         self.csc_rank = [None] * len(self.sizes_k)
         # csc_defer[h]: a strided hop h leaves its index's scan + placement to the fused step's
         # head launch (FusedStep.defer_csc asks for it); csc_deferred[h]: the latest run_hops did
@@ -171,22 +172,6 @@ class DeviceSampler:
         self.meta_fresh[hop] = False          # written by the next run_hops
         return self.edge_meta[hop]
 
-    def index_errors(self):
-        """device int32 tensor: per hop the strided transposed index's sticky error word (1: a
-        block of regnn_ns_hop's index launch gave up waiting for the publish and placed nothing;
-        the index of that batch is incomplete). Reading it is one host sync (check_index). Only
-        the single-launch build (CSC_SPLIT off, CSC_FORK, CSC_FUSE) can raise it: the split
-        build's two launches have no wait between workgroups and never write the word."""
-        return torch.stack([b["tiles"][-1] for b in self.hop_bufs])
-
-    def check_index(self):
-        """raise if any hop's transposed index reported a failed build (index_errors; the split
-        build, CSC_SPLIT, waits on nothing and cannot fail this way)."""
-        bad = self.index_errors().cpu().tolist()
-        if any(bad):
-            raise RuntimeError(f"regnn_ns_hop: the transposed index build timed out waiting for "
-                               f"its publish (hops {[h for h, v in enumerate(bad) if v]})")
-
     def enable_csc(self, hop):
         """also build hop `hop`'s transposed index (regnn_ns_hop csc_*: per local source, its
         edges' target row << 8 | relation), what the fused step's transposed pass gathers by."""
@@ -198,12 +183,10 @@ class DeviceSampler:
         self.csc_rank[hop] = z(ce)
         return self.csc[hop]
 
-    def _csc_args(self, h, split):
-        """regnn_ns_hop's csc_cnt .. csc_rank of hop h (split: with the rank buffer, the
-        two-launch build)"""
+    def _csc_args(self, h):
+        """regnn_ns_hop's csc_cnt .. csc_rank of hop h"""
         c = self.csc[h]
-        args = [L.ptr(t) for t in c] if c is not None else [None] * 4
-        return args + [L.ptr(self.csc_rank[h]) if split and c is not None else None]
+        return [L.ptr(t) for t in (*c, self.csc_rank[h])] if c is not None else [None] * 5
 
     # -- the per-step device work ------------------------------------------------------------
     def batch_from_perm(self, perm, rank=0, world=1):
@@ -212,14 +195,12 @@ class DeviceSampler:
                L.ptr(self.state), L.ptr(self.n_id), L.ptr(self.sizes),
                None if self.stamp_src is None else L.ptr(self.stamp_src), L.stream())
 
-    def run_hops(self, meta_only=True, strided=None, csc_stream=None, before_sums=None):
+    def run_hops(self, meta_only=True, strided=None, before_sums=None):
         """every hop of the current batch; meta_only=False runs hops marked meta_only in full
         (a consumer that reads n_id / the local source ids, e.g. the module path); strided=False
-        writes the CSR blocks whatever self.strided says (None: self.strided). csc_stream
-        (strided): a strided hop's transposed index (and its sampled blk_idx) is built on that
-        stream, forked after the hop's de-duplication, while the next hop samples on this one;
-        the caller joins it. before_sums: called right before the outer hop's sums launch
-        (regnn_ns_hop_typed_sums), e.g. to make it wait on an event."""
+        writes the CSR blocks whatever self.strided says (None: self.strided). before_sums:
+        called right before the outer hop's sums launch (regnn_ns_hop_typed_sums), e.g. to make
+        it wait on an event."""
         strided = self.strided if strided is None else bool(strided)
         # a hop's own layout (hop_strided[h] not None) wins over the call's: the module path
         # samples its outer hop strided with the input sums while hop 0 stays CSR
@@ -229,8 +210,6 @@ class DeviceSampler:
         for h, k in enumerate(self.sizes_k):
             b, blk = self.hop_bufs[h], self.blocks[h]
             sh = hs(h)
-            fork = (csc_stream is not None and sh and self.csc[h] is not None and
-                    self.edge_meta[h] is None)
             if self._sums_path(h, sh, meta_only):
                 if before_sums is not None:
                     before_sums()
@@ -253,57 +232,31 @@ class DeviceSampler:
                            ts["T"], ts["K"],
                            L.ptr(ts["s_agg"]), L.ptr(ts["s_w"]), L.ptr(ts["u_self"]),
                            L.ptr(ts["u_rel"]),
-                           ctypes.addressof(self._csc_job(h - 1, ride_place is not None))
-                           if deferred == h - 1 else None,
+                           ctypes.addressof(self._csc_job(h - 1)) if deferred == h - 1 else None,
                            None if lay is None else ctypes.addressof(lay), L.stream())
                 if ride_place is not None and ride_place[2]:
                     # the ranks rode this launch: hop h - 1's placement follows it on this stream
                     # (the index is complete when run_hops returns)
-                    self._hop_call(ride_place[0], ride_place[1], meta_only, 5, split=True)
+                    self._hop_call(ride_place[0], ride_place[1], meta_only, 5)
                 deferred, ride_place = -1, None
                 self.meta_fresh[h] = not skip
                 self.sums_fresh[h] = True
                 continue
             self.sums_fresh[h] = False
-            # the split index build (counts + ranks, then scan + placement: regnn_ns_hop
-            # csc_rank): what a strided hop with an index and no edge meta runs unless the
-            # single-launch build is asked for (CSC_SPLIT off, or its CSC_FORK / CSC_FUSE forms);
-            # later: the second half left to the fused step's head launch (strided = 4)
-            later = bool(self.csc_defer[h] and sh and self.csc[h] is not None and
-                         self.edge_meta[h] is None and CSC_SPLIT["mode"] != "off")
-            fork = fork and not later
-            split = later or (CSC_SPLIT["mode"] != "off" and not fork and
-                              CSC_FUSE["mode"] == "off")
+            # a strided hop with an index and no edge meta builds it in two halves, neither with a
+            # wait between workgroups (regnn_ns_hop csc_rank: counts + ranks, then scan +
+            # placement); later: the second half left to the fused step's head launch (strided = 4)
+            has_index = bool(sh and self.csc[h] is not None and self.edge_meta[h] is None)
+            later = has_index and bool(self.csc_defer[h])
             self.csc_deferred[h] = later
-            # the transposed index of this hop built beside the next hop's sums (one launch)
-            defer = (not fork and not later and sh and CSC_FUSE["mode"] != "off" and
-                     self.csc[h] is not None and self.edge_meta[h] is None and
-                     h + 1 < len(self.sizes_k) and self._sums_path(h + 1, hs(h + 1), meta_only))
-            # the split build's first half (counts + ranks) in leading workgroups of the next
-            # hop's sums launch (CSC_RIDE; regnn_ns_csc_job kind 1): this call stops after the
-            # de-duplication; the placement follows the sums launch, or is the head launch's
-            ride = (split and not defer and sh and self.csc_ride and
-                    self.csc[h] is not None and self.edge_meta[h] is None and
-                    h + 1 < len(self.sizes_k) and self._sums_path(h + 1, hs(h + 1), meta_only))
-            L.call("regnn_ns_hop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(self.etype_csr),
-                   L.ptr(self.ntype), self.num_edge_types, k, h, L.ptr(self.state),
-                   L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h], L.ptr(self.g2l),
-                   L.ptr(self.first), L.ptr(b["samp"]), L.ptr(b["spos"]), L.ptr(b["scnt"]),
-                   L.ptr(b["gsrc"]), L.ptr(b["flag"]), L.ptr(b["tiles"]), L.ptr(b["status"]),
-                   L.ptr(blk.csr_ptr),
-                   L.ptr(blk.csr_idx), L.ptr(blk.rel), L.ptr(blk.pos), L.ptr(blk.row),
-                   L.ptr(blk.inv),
-                   *((L.ptr(self.local), L.ptr(self.edge_meta[h][0]), L.ptr(self.edge_meta[h][1]))
-                     if self.edge_meta[h] is not None else (None, None, None)),
-                   int(meta_only and self.meta_only[h] and self.edge_meta[h] is not None),
-                   *self._csc_args(h, split),
-                   2 if ride or fork or defer else 4 if later else int(sh), L.stream())
-            deferred = h if defer or ride else -1
+            # the first half in leading workgroups of the next hop's sums launch (CSC_RIDE;
+            # regnn_ns_csc_job): this call stops after the de-duplication (strided = 2); the
+            # placement follows the sums launch, or is the head launch's
+            ride = (has_index and self.csc_ride and h + 1 < len(self.sizes_k) and
+                    self._sums_path(h + 1, hs(h + 1), meta_only))
+            self._hop_call(h, k, meta_only, 2 if ride else 4 if later else int(sh))
+            deferred = h if ride else -1
             ride_place = (h, k, not later) if ride else None
-            if fork:
-                csc_stream.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(csc_stream):
-                    self._hop_call(h, k, meta_only, 3)
             self.meta_fresh[h] = self.edge_meta[h] is not None
         # the blocks now hold the CSR layout (readable by exact_adjs / model_blocks) or not
         self._csr_fresh = not strided
@@ -313,20 +266,19 @@ class DeviceSampler:
         return (self.typed_sums[h] is not None and strided and meta_only and self.meta_only[h]
                 and self.edge_meta[h] is not None)
 
-    def _csc_job(self, h, rank=False):
-        """regnn_ns_csc_job of hop h's transposed index (its buffers are fixed: built once);
-        rank: the counts + ranks job (kind 1) instead of the whole build"""
-        job = self._csc_jobs.get((h, rank))
+    def _csc_job(self, h):
+        """regnn_ns_csc_job of hop h: its index's counts + ranks as a job of the next hop's sums
+        launch (its buffers are fixed: built once)"""
+        job = self._csc_jobs.get((h, True))    # keyed (hop, rank job) as before ABI 51
         if job is None:
             b, blk = self.hop_bufs[h], self.blocks[h]
-            cnt, cptr, cent, clong = self.csc[h]
-            job = self._csc_jobs[(h, rank)] = _NsCscJob(
+            job = self._csc_jobs[(h, True)] = _NsCscJob(
                 h, blk.csr_idx.numel(), L.ptr(b["gsrc"]), L.ptr(self.g2l), L.ptr(blk.csr_idx),
-                L.ptr(blk.row), L.ptr(blk.rel), L.ptr(cnt), L.ptr(b["tiles"]), L.ptr(cptr),
-                L.ptr(cent), L.ptr(clong), L.ptr(self.csc_rank[h]) if rank else None, int(rank))
+                L.ptr(self.csc[h][0]), L.ptr(self.csc_rank[h]))
         return job
 
-    def _hop_call(self, h, k, meta_only, mode, split=False):
+    def _hop_call(self, h, k, meta_only, mode):
+        """regnn_ns_hop of hop h with its buffers; mode: the call's `strided`"""
         rg, b, blk = self.rg, self.hop_bufs[h], self.blocks[h]
         L.call("regnn_ns_hop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(self.etype_csr),
                L.ptr(self.ntype), self.num_edge_types, k, h, L.ptr(self.state),
@@ -338,7 +290,7 @@ class DeviceSampler:
                *((L.ptr(self.local), L.ptr(self.edge_meta[h][0]), L.ptr(self.edge_meta[h][1]))
                  if self.edge_meta[h] is not None else (None, None, None)),
                int(meta_only and self.meta_only[h] and self.edge_meta[h] is not None),
-               *self._csc_args(h, split), mode, L.stream())
+               *self._csc_args(h), mode, L.stream())
 
     def set_seed(self, base_seed, epoch, batch_idx):
         """host-driven batches (the PyG-style iterator): seed words + a fresh dedup stamp."""
@@ -444,9 +396,7 @@ CSC_LONG_INTS = ((_LONG_CAP + 2) + 3) // 4 * 4 + 4 * _MAX_PIECE
 class _NsCscJob(ctypes.Structure):
     """regnn_ns_csc_job (include/regnn_hip.h)."""
     _fields_ = [("hop", ctypes.c_int32), ("cap_e", ctypes.c_int32), ("gsrc", _P), ("g2l", _P),
-                ("blk_idx", _P), ("blk_row", _P), ("blk_rel", _P), ("csc_cnt", _P),
-                ("tiles", _P), ("csc_ptr", _P), ("csc_ent", _P), ("csc_long", _P),
-                ("csc_rank", _P), ("kind", ctypes.c_int32)]
+                ("blk_idx", _P), ("csc_cnt", _P), ("csc_rank", _P)]
 
 
 class _NsmAdam(ctypes.Structure):
@@ -594,32 +544,19 @@ MODULE_AHEAD = {"n": int(os.environ.get("REGNN_NS_MODULE_AHEAD", "8"))}
 # one launch; the loss backward with out_lin's bias gradient in one); "off": out_lin, ns_labels
 # and ops.softmax_xent (A/B)
 LIN_XENT = {"mode": os.environ.get("REGNN_NS_LIN_XENT", "on")}
-# "on": the pipelined fused engine builds hop 0's transposed index on a third stream while hop 1
-# samples (regnn_ns_hop strided 2 / 3); "off" (default): in the sampler's own chain. Eager runs
-# are fine; capturing the third stream (forked from the sampler's stream, joined back before the
-# next batch) segfaults inside torch.cuda.graph's capture_end on this image (ROCm 7.2, torch
-# 2.10), so the graphed bench cannot use it
-CSC_FORK = {"mode": os.environ.get("REGNN_NS_CSC_FORK", "off")}
-# "on": hop 0's transposed index is built by extra workgroups of the outer hop's sums launch
-# (regnn_ns_hop_typed_sums csc), beside the sums instead of ahead of them in the sampler's
-# chain; "off" (default): its own launch after hop 0's de-duplication. Measured (interleaved,
-# 300 steps): 111.1-111.5 us on against 107.7-108.4 off -- the sampler's chain is not what
-# bounds the step; its waiting workgroups beside the model's kernels cost more than they save
-CSC_FUSE = {"mode": os.environ.get("REGNN_NS_CSC_FUSE", "off")}
-# "on" (default): a strided hop's transposed index in two launches with no wait between
-# workgroups (regnn_ns_hop csc_rank: counts + ranks, then every workgroup's own scan and
-# placement); "off": the single launch whose last block scans while the others spin (A/B)
-CSC_SPLIT = {"mode": os.environ.get("REGNN_NS_CSC_SPLIT", "on")}
-# "on": the fused trainer's hop 0 runs the split build's first launch only and the step's head
+# A strided hop's transposed index is built in two halves with no wait between workgroups
+# (regnn_ns_hop csc_rank: counts + ranks, then every workgroup's own scan and placement); the two
+# knobs below choose where the halves run. DESIGN section 4b has the measurements
+# "on": the fused trainer's hop 0 runs the build's first half only and the step's head
 # launch finishes the index on CUs it leaves idle (regnn_nsm_work csc_pending); "off": the
 # placement on the sampler's queue; "auto" (default): "on" where hop 0's counts + ranks ride the
 # sums launch (CSC_RIDE: the placement would otherwise be one more launch after the sums, and the
 # sampler's chain per batch ends with the sums launch instead), else "off" (with the rank launch
-# of its own the deferral measured within noise). DESIGN section 4b has the measurements
+# of its own the deferral measured within noise)
 CSC_DEFER = {"mode": os.environ.get("REGNN_NS_CSC_DEFER", "auto")}
-# "on" (default): where a strided hop's split build is followed by the sums launch (the fused
+# "on" (default): where a strided hop's index build is followed by the sums launch (the fused
 # trainer's hop 0), its counts + ranks run in leading workgroups of that launch instead of a
-# launch of their own (regnn_ns_csc_job kind 1: a slot per thread, no wait), and the placement
+# launch of their own (regnn_ns_csc_job: a slot per thread, no wait), and the placement
 # follows the sums launch (or rides the head launch, CSC_DEFER); "off": the rank launch of its
 # own ahead of the sums. Every other hop sequence is the same either way
 CSC_RIDE = {"mode": os.environ.get("REGNN_NS_CSC_RIDE", "on")}
@@ -652,10 +589,9 @@ def default_ahead(world):
 # placing it beside step i's agg0 / head; N: only every N-th batch (each edge costs a
 # marker on the model's queue, ~4 us of idle before the next agg0; 6 x 20-step runs: on 111.0,
 # 2 110.1, 4 110.2 us; 160 steps 106.2 / 105.5 / 105.5); "off": the sampler runs free
-# "auto" (default): "on" where hop 0's transposed index is the split build (CSC_SPLIT, deferred
-# or not: the sampler's chain per batch is then 7-15 us shorter and reaches every step's edge in
-# time, so each sums launch sits beside agg0 / head), else "2" (with the single-launch index
-# "on" measured 100.2-100.6 against 99.3-99.8). DESIGN section 4b has the runs
+# "auto" (default): "on" where the fused trainer's strided hop 0 builds a transposed index (in
+# two halves, deferred or not: the sampler's chain per batch reaches every step's edge in time,
+# so each sums launch sits beside agg0 / head), else "2". DESIGN section 4b has the runs
 SUMS_ALIGN = {"mode": os.environ.get("REGNN_NS_SUMS_ALIGN", "auto")}
 # "on": the module path sizes its GEMMs' split-K for the first batch's live rows (ops.LIVE_HINT:
 # ~6 k of the 13312-row capacity at mag-10x, split 2 with a reduce); measured at hidden 512 (3 x
@@ -960,9 +896,9 @@ class FusedStep:
         queue (CSC_DEFER): the sampler's strided hop 0 then writes counts and ranks only
         (regnn_ns_hop strided = 4; with CSC_RIDE the outer hop's sums launch writes them and
         hop 0 stops after its de-duplication) and the step runs with csc_pending. Returns whether it
-        applies: the two-layer step over strided blocks, the split build, neither CSC_FORK nor
-        CSC_FUSE, and the scan's LDS under the head launch's limit (else both launches stay on
-        the sampler's queue). No path here can raise the index's error word (index_errors)."""
+        applies: the two-layer step over strided blocks with hop 0's index and no edge meta, and
+        the scan's LDS under the head launch's limit (else both launches stay on the sampler's
+        queue)."""
         s, W = self.sampler, self.W
         ce = s.blocks[0].csr_idx.numel()
         mode = CSC_DEFER["mode"]
@@ -970,9 +906,7 @@ class FusedStep:
             mode = "on" if (s.csc_ride and len(s.sizes_k) > 1 and
                             s._sums_path(1, True, True)) else "off"
         ok = (self.two_layer and s.strided and s.csc[0] is not None and
-              s.edge_meta[0] is None and
-              CSC_SPLIT["mode"] != "off" and mode != "off" and
-              CSC_FORK["mode"] == "off" and CSC_FUSE["mode"] == "off" and
+              s.edge_meta[0] is None and mode != "off" and
               (ce + 64) * 4 <= _HEAD_LDS_MAX and
               # the index's grid row is no wider than the head's own (ceil(cap0 / 16) blocks of
               # 16 rows): only a fan-out of 64 exceeds it, and regnn_nsm_step refuses that
@@ -1124,11 +1058,23 @@ def warm_walk(ahead, n_slots):
     return out
 
 
+@contextlib.contextmanager
 def _capturing(g):
     """capture into g with the thread-local error mode: with several ranks the process group's
     watchdog thread polls the eager all-reduces' events meanwhile, which the global mode counts
-    as an illegal call during capture (it invalidates the capture at random)."""
-    return torch.cuda.graph(g, capture_error_mode="thread_local")
+    as an illegal call during capture (it invalidates the capture at random). Python's cyclic
+    collector is held off until the capture has ended: torch.cuda.graph does not collect on
+    entry, so a dead reference cycle from earlier (e.g. a trainer kept by a traceback, with its
+    graphs and their pool memory) could otherwise be finalised in the middle of the capture,
+    which aborts the process."""
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            yield
+    finally:
+        if collecting:
+            gc.enable()
 
 
 def early_grad_params(model):
@@ -1322,8 +1268,6 @@ class NSTrainer:
                                            priority=int(os.environ.get("REGNN_NS_SIDE_PRIORITY", "0")))
             self._sides = [self._side] + [torch.cuda.Stream(device=dev)
                                           for _ in range(self.lanes - 1)]
-            if self.fused is not None and CSC_FORK["mode"] != "off":
-                self._csc = torch.cuda.Stream(device=dev)
         # one rank, FlatAdam, two-layer step: the optimizer runs inside the step's last launch
         # (no all-reduce sits between the backward and the update)
         self.adam_fused = (self.fused is not None and self.fused.two_layer and self.world == 1
@@ -1473,13 +1417,7 @@ class NSTrainer:
         s = self.slots[slot]
         s.batch_from_perm(self.perm, self.rank + slot * self.world, n * self.world)
         if self.fused is not None:
-            # the pipelined engine builds hop 0's transposed index on a third stream while hop 1
-            # samples (CSC_FORK), joined back right after: the next batch's sampling writes the
-            # dedup tables (g2l) every slot shares, which the index reads
-            csc = getattr(self, "_csc", None)
-            s.run_hops(csc_stream=csc, before_sums=before_sums)
-            if csc is not None:
-                torch.cuda.current_stream(self.device).wait_stream(csc)
+            s.run_hops(before_sums=before_sums)
         else:                                 # the module path reads the CSR blocks
             s.run_hops(meta_only=self._module_lean, strided=False)
 
@@ -1526,10 +1464,8 @@ class NSTrainer:
         mode = SUMS_ALIGN["mode"]
         if mode == "auto":
             s0 = self.slots[0]
-            split = (self.fused is not None and s0.strided and s0.csc[0] is not None and
-                     CSC_SPLIT["mode"] != "off" and CSC_FORK["mode"] == "off" and
-                     CSC_FUSE["mode"] == "off")
-            mode = "on" if split else "2"
+            mode = "on" if (self.fused is not None and s0.strided and
+                            s0.csc[0] is not None) else "2"
         every = 0 if mode == "off" or self.fused is None else (1 if mode == "on" else int(mode))
         align = every > 0
         ends = {}
@@ -2010,12 +1946,4 @@ class NSTrainer:
     def edges_total(self):
         """aggregated edges of every batch sampled so far (device counters: one host sync;
         pipelined, that includes the batch sampled ahead)."""
-        # one host sync: the slots' edge counters and (the sampler's own failure report riding
-        # on it) every slot's transposed-index error words
-        words = torch.cat([torch.stack([s.state[5] for s in self.slots]).sum().reshape(1)] +
-                          [s.index_errors().to(torch.int64) for s in self.slots]).cpu().tolist()
-        if any(words[1:]):
-            bad = [i for i, s in enumerate(self.slots) if any(s.index_errors().cpu().tolist())]
-            raise RuntimeError(f"regnn_ns_hop: a transposed index build timed out waiting for its "
-                               f"publish (sampler slots {bad}): those batches are incomplete")
-        return int(words[0])
+        return int(torch.stack([s.state[5] for s in self.slots]).sum().item())

@@ -51,7 +51,7 @@ def test_symbol_and_abi():
     old, _ = _lib._SIG["regnn_ns_hop_typed_sums"]
     # the fp32 entry's parameters in its order, with dtype right after tables (position 17)
     assert args == old[:18] + [ctypes.c_int32] + old[18:] and ret is ctypes.c_int
-    assert _lib._so.regnn_abi_version() == _lib.ABI_VERSION == build.header_abi() == 50
+    assert _lib._so.regnn_abi_version() == _lib.ABI_VERSION == build.header_abi() == 51
     assert (_lib.F32_CODE, _lib.BF16_CODE) == (F32, BF16)
 
 
