@@ -895,7 +895,8 @@ typedef struct regnn_nsm_params {
     float* g_ln_b[REGNN_NSM_MAX_LAYERS];
     float* g_out_w;
     float* g_out_b;
-    float* loss;              /* [1]: mean nll over the batch targets with a label >= 0 */
+    float* loss;              /* [1]: mean nll over the batch targets with a label >= 0; with no
+                                 such target 0, and every gradient 0 (not a NaN mean) */
     int32_t n_edge_types;     /* relations < n_edge_types are edges; n_edge_types + type: self loops */
     int32_t rel_slots;        /* 1: every (target type, source type) pair has at most one edge
                                  relation (the caller checked the graph once): layer 0 sums its

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import _golden as G
+from _nsm_ref import nsm_seed as _nsm_seed   # the fused step's per-layer dropout seed
 from oracle import sampler_oracle as SO
 
 pytestmark = pytest.mark.gpu
@@ -426,14 +427,6 @@ def _sample_row_global(row_idx, t, k, seed, base):
         chosen.append(j if pos in chosen else pos)
     chosen.sort()
     return [int(row_idx[p]) for p in chosen], [base + p for p in chosen]
-
-
-def _nsm_seed(st, layer):
-    """the fused step's dropout seed of `layer` (include/regnn_hip.h, regnn_nsm_step): seed
-    word, epoch and global batch of the step's sampler state."""
-    from regnn_hip.sampler import _mix
-    M = (1 << 64) - 1
-    return _mix((st[0] & M) ^ _mix(((st[1] << 40) ^ (st[3] << 8) ^ (layer + 0x51ED27)) & M))
 
 
 @pytest.mark.parametrize("rel_slots", ["auto", "off"])
