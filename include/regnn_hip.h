@@ -20,8 +20,8 @@
  *  - Segments with more than `split` edges are processed by the long-segment plan
  *    (long_ids/chunk_long/chunk_off, see regnn_spmm_fwd) so hubs do not serialise one wave;
  *    split == 0 disables splitting. Results are bitwise reproducible run to run: no float
- *    atomics (except regnn_ns_spmm_bwd, the sampled-block backward); cross-block reductions go
- *    through fixed-order slabs.
+ *    atomics (except regnn_ns_spmm_bwd and regnn_ns_gat_bwd, the sampled-block backwards);
+ *    cross-block reductions go through fixed-order slabs.
  */
 #ifndef REGNN_HIP_H
 #define REGNN_HIP_H
@@ -776,6 +776,62 @@ int regnn_ns_spmm_bwd_csc(const int32_t* csc_ptr, const int32_t* csc_ent, const 
                           const float* x, float* gx, float* slab, int32_t n_rel,
                           const int32_t* sizes, int32_t size_idx, int64_t cap_rows, int32_t F,
                           int32_t slab_rows, float* hub_work, hipStream_t stream);
+
+/* mag REGATConv attention over one device-sampled block, read as regnn_ns_hop leaves it (the CSR
+ * layout: ptr [cap_dst + 1], idx / rel [cap_e], rows past the batch's live ones empty; no host
+ * size anywhere, so a step with it can be captured). Replaces, for such a block, the reference's
+ * mag/regnn_layers.py:253-273 with the softmax of mag/utils.py:45-57 (the exact-size path's
+ * regnn_gat_scores -> amax -> regnn_edge_softmax_fwd -> regnn_spmm_heads_fwd chain):
+ *   s[e,h]     = LeakyReLU_slope((el[idx_e,h] + er[v,h]) + tab[rel_e,h])      v = the row of e
+ *   gmax       = max of s over every entry and head (ONE scalar, formed on the device)
+ *   a[e,h]     = exp(s[e,h] - gmax) / (sum_{e' in row v} exp(s[e',h] - gmax) + 1e-16)
+ *   out[v,h,:] = sum_{e in row v} a[e,h] ft[idx_e,h,:]
+ * el [>= n_src, H], er [cap_dst, H], tab [n_rel, H] (NULL: no relation term; rel then unread),
+ * ft [>= n_src, H, C], a [cap_e, H] (saved for the backward), out [cap_dst, H, C]; all fp32,
+ * ft / out / gy / g_ft rows 16-byte aligned. The maximum is global on purpose (a row far below it
+ * underflows to a = 0 exactly as regnn_edge_softmax_fwd(gmax, 1e-16) does). Two launches: the
+ * scores (into a) with one maximum per workgroup into work (REGNN_NS_GAT_WORK_FLOATS floats,
+ * every used slot rewritten by every call: nothing to reset between replays of a captured graph),
+ * then every wave folds those maxima (order-free) and takes a row: the denominators and out are
+ * summed in entry order (64 entries in LDS at a time, any row length), bitwise reproducible.
+ * Rows without entries get exact zeros in out. An entry whose idx lies outside [0, n_src) takes
+ * no part (weight 0).
+ *
+ * Backward (one launch), the documented one of the global-max softmax: the maximum is a constant
+ * and the 1e-16 stays in the denominator. With ga[e,h] = <gy[v,h,:], ft[idx_e,h,:]> and
+ * D[v,h] = sum_row a ga:
+ *   gs = a (ga - D);  gl = gs * (pre-activation > 0 ? 1 : slope)     (the sign recomputed)
+ *   g_er[v,h] = sum_row gl (every row written; empty rows 0)
+ *   slab[b][r,h] (optional, with tab) = workgroup b's partial of sum_{rel_e = r} gl -- exactly
+ *     slab_rows workgroups are launched and each writes its row (no zero fill needed); reduce
+ *     with regnn_rel_reduce(slab, slab_rows, n_rel * H). n_rel * H <= REGNN_NS_GAT_MAX_BINS,
+ *     slab_rows <= REGNN_NS_GAT_WORK_FLOATS.
+ *   g_el[u,h] += gl,  g_ft[u,h,:] += a[e,h] gy[v,h,:]   over the entries with idx_e = u
+ * D, g_er and the slab are summed in entry order (per wave, the waves' bins in wave order):
+ * bitwise reproducible. The per-source sums take form (b): hardware float atomics into g_ft /
+ * g_el ZERO-FILLED BY THE CALLER, for every block -- the outer hop's block (~280 k entries) has
+ * no transposed index, and one form keeps one kernel; the same documented exception as
+ * regnn_ns_spmm_bwd (the summation order is run-dependent). Each g_ft atomic wave-instruction adds
+ * 64 consecutive columns of one source row (256 contiguous bytes). Rows u the block never names
+ * (u >= sizes[hop + 1]) keep the caller's zeros. A gather over hop 0's transposed index (form (a))
+ * is not built.
+ *
+ * 1 <= H <= 16, C % 4 == 0, 4 <= C <= 512, else REGNN_EUNSUPPORTED; a NULL required pointer (or
+ * tab without rel, slab without tab) REGNN_EINVAL; both before any launch.
+ * Added without an ABI bump (the version stays 51): two new symbols, no existing prototype,
+ * struct or behaviour moves, so every caller built against ABI 51 runs unchanged, and the
+ * version pins of the build and its tests keep their meaning. */
+#define REGNN_NS_GAT_WORK_FLOATS 2048
+#define REGNN_NS_GAT_MAX_BINS 1024
+int regnn_ns_gat_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel, const float* el,
+                     const float* er, const float* tab, const float* ft, float slope,
+                     int64_t cap_dst, int64_t n_src, int32_t H, int32_t C, float* a, float* out,
+                     float* work, hipStream_t stream);
+int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel, const float* el,
+                     const float* er, const float* tab, const float* ft, const float* a,
+                     const float* gy, float slope, int64_t cap_dst, int64_t n_src, int32_t H,
+                     int32_t C, int32_t n_rel, float* g_ft, float* g_el, float* g_er, float* slab,
+                     int32_t slab_rows, hipStream_t stream);
 
 /* Typed aggregation of raw input rows over a sampled block (layer 0 of the NS REGNN at any hidden
  * width; mag/regnn_ns.py:300-326 group_input + mag/regnn_layers.py:101-148, replacing the

@@ -1,0 +1,350 @@
+// mag REGATConv attention over one device-sampled block as the sampler leaves it (regnn_ns_hop's
+// capacity-sized CSR: ptr [cap_dst + 1], idx / rel [cap_e], rows past the live ones empty):
+// mag/regnn_layers.py:253-273 with the softmax of mag/utils.py:45-57 (ONE maximum over every live
+// entry and head, + 1e-16 in the denominator). No host size anywhere: a row is live when it has
+// entries. Rows are short (fan-out <= 64 plus the self loop), so a wave takes a row, holds up to
+// 64 of its entries in LDS and loops in entry order past that; there is no long-segment plan.
+//
+//   launch 1  ns_gat_score_kernel   s[e,h] into the `a` buffer, one maximum per workgroup
+//   launch 2  ns_gat_fwd_kernel     every wave folds the workgroup maxima (a maximum does not
+//                                   depend on the order; every slot is rewritten each call, so a
+//                                   replayed graph needs no reset), den in entry order, a, out
+//   backward  ns_gat_bwd_kernel     ga, D, gs, gl per row; g_er and the relation slab in entry
+//                                   order; g_el / g_ft by float atomics (form (b), regnn_hip.h)
+#include "regnn_common.h"
+
+#include <math.h>
+
+namespace regnn {
+namespace {
+
+constexpr int kChunk = 64;                  // entries of a row held in LDS at a time
+constexpr int kMaxHeads = 16;
+constexpr int kWaves = kBlock / 64;
+
+// LDS written by some lanes of this wave, read by others: the wave's own LDS traffic in order
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+__device__ __forceinline__ float wave_maxf(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// an entry whose source id lies outside [0, n_src) takes no part: score -inf, weight 0
+__device__ __forceinline__ bool src_ok(int u, int64_t n_src) {
+    return u >= 0 && int64_t(u) < n_src;
+}
+
+__device__ __forceinline__ float pre_act(const float* __restrict__ el, const float* __restrict__ er,
+                                         const float* __restrict__ tab, int u, int64_t v, int r,
+                                         int H, int h) {
+    const float x = el[int64_t(u) * H + h] + er[v * H + h];
+    return tab ? x + tab[r * H + h] : x;
+}
+
+__global__ void __launch_bounds__(kBlock)
+ns_gat_score_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                    const uint8_t* __restrict__ rel, const float* __restrict__ el,
+                    const float* __restrict__ er, const float* __restrict__ tab, float slope,
+                    int64_t n_rows, int64_t n_src, int H, float* __restrict__ s,
+                    float* __restrict__ wgmax) {
+    __shared__ float smax[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float m = -INFINITY;
+    for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
+         v += int64_t(gridDim.x) * kWaves) {
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        const int n = (e1 - e0) * H;
+        for (int i = lane; i < n; i += 64) {
+            const int j = i / H, h = i - j * H;
+            const int e = e0 + j;
+            const int u = idx[e];
+            float x = -INFINITY;
+            if (src_ok(u, n_src)) {
+                x = pre_act(el, er, tab, u, v, tab ? rel[e] : 0, H, h);
+                x = x > 0.f ? x : x * slope;
+                m = fmaxf(m, x);
+            }
+            s[int64_t(e) * H + h] = x;
+        }
+    }
+    m = wave_maxf(m);
+    if (lane == 0) smax[wave] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float b = smax[0];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) b = fmaxf(b, smax[w]);
+        wgmax[blockIdx.x] = b;                 // every workgroup, every call
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+ns_gat_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                  const float* __restrict__ ft, const float* __restrict__ wgmax, int n_wg,
+                  int64_t n_rows, int64_t n_src, int H, int C, float* __restrict__ a,
+                  float* __restrict__ out) {
+    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
+    __shared__ int su_[kWaves][kChunk];
+    __shared__ float sden_[kWaves][kMaxHeads];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* sa = sa_[wave];
+    int* su = su_[wave];
+    float* sden = sden_[wave];
+    float gmax = -INFINITY;
+    for (int i = lane; i < n_wg; i += 64) gmax = fmaxf(gmax, wgmax[i]);
+    gmax = wave_maxf(gmax);
+    const int HC = H * C, nvec = HC >> 2;
+    for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
+         v += int64_t(gridDim.x) * kWaves) {
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        float* orow = out + v * HC;
+        if (e1 <= e0) {                        // a padded row: exact zeros
+            for (int c = lane; c < nvec; c += 64)
+                *reinterpret_cast<float4*>(orow + 4 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        wave_lds_sync();                       // the previous row's reads of sden are done
+        if (lane < H) {                        // the row's denominators, in entry order
+            float den = 0.f;
+            for (int e = e0; e < e1; ++e) {
+                const float sv = a[int64_t(e) * H + lane];
+                den += sv == -INFINITY ? 0.f : expf(sv - gmax);
+            }
+            sden[lane] = den;
+        }
+        for (int t0 = 0; t0 < nvec; t0 += 64) {
+            const int c4 = t0 + lane;
+            const bool active = c4 < nvec;
+            const int h = active ? (4 * c4) / C : 0;
+            const bool last = t0 + 64 >= nvec;     // this pass replaces s by a in the buffer
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int cb = e0; cb < e1; cb += kChunk) {
+                const int nc = min(kChunk, e1 - cb);
+                wave_lds_sync();               // sden written; the previous chunk read
+                for (int i = lane; i < nc * H; i += 64) {
+                    const int j = i / H, hh = i - j * H;
+                    const int64_t at = int64_t(cb + j) * H + hh;
+                    // (rows wider than 64 vectors take several passes: all but the last leave s
+                    // in the buffer and form the same a from it again)
+                    const float sv = a[at];
+                    const float w = (sv == -INFINITY ? 0.f : expf(sv - gmax)) /
+                                    (sden[hh] + 1e-16f);
+                    if (last) a[at] = w;
+                    sa[i] = w;
+                }
+                for (int j = lane; j < nc; j += 64) {
+                    const int u = idx[cb + j];
+                    su[j] = src_ok(u, n_src) ? u : -1;
+                }
+                wave_lds_sync();
+                if (active) {
+#pragma unroll 4
+                    for (int j = 0; j < nc; ++j) {
+                        const int u = su[j];
+                        if (u < 0) continue;
+                        const float w = sa[j * H + h];
+                        const float4 x = *reinterpret_cast<const float4*>(
+                            ft + int64_t(u) * HC + 4 * c4);
+                        acc.x = fmaf(w, x.x, acc.x);
+                        acc.y = fmaf(w, x.y, acc.y);
+                        acc.z = fmaf(w, x.z, acc.z);
+                        acc.w = fmaf(w, x.w, acc.w);
+                    }
+                }
+            }
+            if (active) *reinterpret_cast<float4*>(orow + 4 * c4) = acc;
+        }
+    }
+}
+
+// One wave per row. Pass 1 over the row's chunks: ga[e,h] = <gy[v,h,:], ft[u,h,:]> (a lane per
+// (entry, head), columns in order) and D[v,h] = sum a ga in entry order. Pass 2: gs, gl (the
+// pre-activation's sign recomputed from el + er + tab), g_er and the wave's relation bins by lane
+// h in entry order, g_el and g_ft by atomics -- g_ft as one instruction per 64 consecutive
+// columns of a source row (256 contiguous bytes). A row of more than one chunk recomputes ga in
+// pass 2 (the same instructions on the same operands: the same bits).
+__global__ void __launch_bounds__(kBlock)
+ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                  const uint8_t* __restrict__ rel, const float* __restrict__ el,
+                  const float* __restrict__ er, const float* __restrict__ tab,
+                  const float* __restrict__ ft, const float* __restrict__ a,
+                  const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src, int H,
+                  int C, int n_rel, float* __restrict__ g_ft, float* __restrict__ g_el,
+                  float* __restrict__ g_er, float* __restrict__ slab) {
+    extern __shared__ float bins_[];           // [kWaves][n_rel * H] when slab
+    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
+    __shared__ float sg_[kWaves][kChunk * kMaxHeads];
+    __shared__ int su_[kWaves][kChunk];
+    __shared__ int sr_[kWaves][kChunk];
+    __shared__ float sD_[kWaves][kMaxHeads];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* sa = sa_[wave];
+    float* sg = sg_[wave];
+    int* su = su_[wave];
+    int* sr = sr_[wave];
+    float* sD = sD_[wave];
+    const int W = n_rel * H;
+    float* bins = bins_ + wave * W;
+    if (slab) {
+        for (int i = threadIdx.x; i < kWaves * W; i += kBlock) bins_[i] = 0.f;
+        __syncthreads();
+    }
+    const int HC = H * C;
+    for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
+         v += int64_t(gridDim.x) * kWaves) {
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        if (e1 <= e0) {
+            if (lane < H) g_er[v * H + lane] = 0.f;
+            continue;
+        }
+        const float* gyr = gy + v * HC;
+        // the chunk [cb, cb + nc): ids, a and ga into LDS
+        auto fill = [&](int cb, int nc) {
+            wave_lds_sync();
+            for (int j = lane; j < nc; j += 64) {
+                const int u = idx[cb + j];
+                su[j] = src_ok(u, n_src) ? u : -1;
+                sr[j] = tab ? int(rel[cb + j]) : 0;
+            }
+            for (int i = lane; i < nc * H; i += 64) {
+                const int j = i / H, hh = i - j * H;
+                const int u = idx[cb + j];
+                float d = 0.f, w = 0.f;
+                if (src_ok(u, n_src)) {
+                    w = a[int64_t(cb + j) * H + hh];
+                    const float4* gp = reinterpret_cast<const float4*>(gyr + hh * C);
+                    const float4* xp = reinterpret_cast<const float4*>(
+                        ft + int64_t(u) * HC + hh * C);
+                    for (int c = 0; c < (C >> 2); ++c) {
+                        const float4 g = gp[c], x = xp[c];
+                        d = fmaf(g.x, x.x, d);
+                        d = fmaf(g.y, x.y, d);
+                        d = fmaf(g.z, x.z, d);
+                        d = fmaf(g.w, x.w, d);
+                    }
+                }
+                sa[i] = w;
+                sg[i] = d;
+            }
+            wave_lds_sync();
+        };
+        const bool one = e1 - e0 <= kChunk;
+        float D = 0.f;
+        for (int cb = e0; cb < e1; cb += kChunk) {
+            const int nc = min(kChunk, e1 - cb);
+            fill(cb, nc);
+            if (lane < H)
+                for (int j = 0; j < nc; ++j) D = fmaf(sa[j * H + lane], sg[j * H + lane], D);
+        }
+        if (lane < H) sD[lane] = D;
+        float ger = 0.f;
+        for (int cb = e0; cb < e1; cb += kChunk) {
+            const int nc = min(kChunk, e1 - cb);
+            if (!one) fill(cb, nc);
+            else wave_lds_sync();              // sD written
+            for (int i = lane; i < nc * H; i += 64) {
+                const int j = i / H, hh = i - j * H;
+                const int u = su[j];
+                float gl = 0.f;
+                if (u >= 0) {
+                    const float gs = sa[i] * (sg[i] - sD[hh]);
+                    gl = pre_act(el, er, tab, u, v, sr[j], H, hh) > 0.f ? gs : gs * slope;
+                    unsafeAtomicAdd(g_el + int64_t(u) * H + hh, gl);
+                }
+                sg[i] = gl;                    // (this lane's own slot)
+            }
+            wave_lds_sync();
+            if (lane < H) {
+                for (int j = 0; j < nc; ++j) {
+                    const float gl = sg[j * H + lane];
+                    ger += gl;
+                    const int r = sr[j];
+                    if (slab && r < n_rel) bins[r * H + lane] += gl;
+                }
+            }
+            for (int col = lane; col < HC; col += 64) {
+                const int h = col / C;
+                const float g = gyr[col];
+                for (int j = 0; j < nc; ++j) {
+                    const int u = su[j];
+                    if (u >= 0) unsafeAtomicAdd(g_ft + int64_t(u) * HC + col, sa[j * H + h] * g);
+                }
+            }
+        }
+        if (lane < H) g_er[v * H + lane] = ger;
+    }
+    if (!slab) return;
+    __syncthreads();
+    for (int i = threadIdx.x; i < W; i += kBlock) {
+        float t = bins_[i];                    // the waves' bins in wave order
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) t += bins_[w * W + i];
+        slab[int64_t(blockIdx.x) * W + i] = t;
+    }
+}
+
+inline int shape_rc(int32_t H, int32_t C) {
+    if (H < 1 || H > kMaxHeads || C < 4 || C > 512 || (C & 3)) return REGNN_EUNSUPPORTED;
+    return REGNN_OK;
+}
+
+inline int ns_gat_grid(int64_t cap_dst) {
+    const int64_t g = (cap_dst + kWaves - 1) / kWaves;
+    return int(g < 1 ? 1 : g < REGNN_NS_GAT_WORK_FLOATS ? g : REGNN_NS_GAT_WORK_FLOATS);
+}
+
+}  // namespace
+}  // namespace regnn
+
+using namespace regnn;
+
+extern "C" int regnn_ns_gat_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                                const float* el, const float* er, const float* tab,
+                                const float* ft, float slope, int64_t cap_dst, int64_t n_src,
+                                int32_t H, int32_t C, float* a, float* out, float* work,
+                                hipStream_t stream) {
+    if (!ptr || !idx || !el || !er || !ft || !a || !out || !work || (tab && !rel) ||
+        cap_dst < 0 || n_src < 0)
+        return REGNN_EINVAL;
+    if (const int rc = shape_rc(H, C)) return rc;
+    if (cap_dst == 0) return REGNN_OK;
+    const int grid = ns_gat_grid(cap_dst);
+    hipLaunchKernelGGL(ns_gat_score_kernel, dim3(grid), dim3(kBlock), 0, stream, ptr, idx, rel,
+                       el, er, tab, slope, cap_dst, n_src, int(H), a, work);
+    REGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ns_gat_fwd_kernel, dim3(grid), dim3(kBlock), 0, stream, ptr, idx, ft,
+                       static_cast<const float*>(work), grid, cap_dst, n_src, int(H), int(C), a,
+                       out);
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}
+
+extern "C" int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                                const float* el, const float* er, const float* tab,
+                                const float* ft, const float* a, const float* gy, float slope,
+                                int64_t cap_dst, int64_t n_src, int32_t H, int32_t C,
+                                int32_t n_rel, float* g_ft, float* g_el, float* g_er, float* slab,
+                                int32_t slab_rows, hipStream_t stream) {
+    if (!ptr || !idx || !el || !er || !ft || !a || !gy || !g_ft || !g_el || !g_er ||
+        (tab && !rel) || (slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 ||
+        (tab && n_rel < 1) || (slab && slab_rows < 1))
+        return REGNN_EINVAL;
+    if (const int rc = shape_rc(H, C)) return rc;
+    if (slab && (int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS || slab_rows > REGNN_NS_GAT_WORK_FLOATS))
+        return REGNN_EUNSUPPORTED;
+    if (cap_dst == 0 && !slab) return REGNN_OK;
+    // with a slab the launch has exactly slab_rows workgroups: each writes its row
+    const int grid = slab ? int(slab_rows) : ns_gat_grid(cap_dst);
+    const size_t lds = slab ? size_t(kWaves) * n_rel * H * sizeof(float) : 0;
+    hipLaunchKernelGGL(ns_gat_bwd_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx, rel, el,
+                       er, tab, ft, a, gy, slope, cap_dst, n_src, int(H), int(C), int(n_rel), g_ft,
+                       g_el, g_er, slab);
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}

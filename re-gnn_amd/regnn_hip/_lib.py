@@ -111,6 +111,9 @@ _SIG = {
     "regnn_ns_csc_hub_work_floats": ([I32], I64),
     "regnn_ns_spmm_bwd_csc": ([P, P, P, P, P, P, P, P, P, I32, P, I32, I64, I32, I32, P, P],
                               ctypes.c_int),
+    "regnn_ns_gat_fwd": ([P, P, P, P, P, P, P, F32, I64, I64, I32, I32, P, P, P, P], ctypes.c_int),
+    "regnn_ns_gat_bwd": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P,
+                          I32, P], ctypes.c_int),
     "regnn_ns_typed_agg": ([P, P, P, P, P, P, P, P, P, P, I32, I32, I64, P, P, I64, I64, P],
                            ctypes.c_int),
     "regnn_ns_typed_agg_bwd": ([P, P, P, P, P, P, P, P, P, I32, I32, I64, P, P, I64, I64, P, I32,

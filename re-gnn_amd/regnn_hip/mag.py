@@ -180,7 +180,8 @@ class REGATConv(torch.nn.Module):
     Scores LeakyReLU(rw[type] + att_src.x_src[u] + att_dst.x_dst[v]) and the ogbn-mag softmax
     (one global max, + 1e-16, mag/utils.py:45-57) run as HIP kernels (regnn_gat_scores,
     regnn_edge_softmax_fwd; backward regnn_gat_softmax_bwd + segment sums), the aggregation as
-    the HIP per-head SpMM."""
+    the HIP per-head SpMM. On a device-sampled NSBlock (edge_index = the block) all of it is
+    ops.ns_gat (regnn_ns_gat_fwd / _bwd) over the block as the sampler left it."""
 
     v2 = False
 
@@ -230,23 +231,57 @@ class REGATConv(torch.nn.Module):
         return ops.gat_attention(rg, a_s, a_d, tab, pack, self.negative_slope,
                                  global_max=True)                           # :298-307
 
+    def _block_attention(self, blk, x_src, x_dst, tab, n_dst, return_weights):
+        """out [n_dst, H, C] over a device-sampled NSBlock (self_loop_type 2: the sampler's
+        blocks carry the targets' self loops with relation num_edge_types + node type)."""
+        if return_weights:
+            raise ValueError("return_weights needs the edge_index / edge_type tensors, not a "
+                             "device-sampled block")
+        if self.self_loop_type != 2:
+            raise ValueError("a device-sampled block holds self_loop_type 2's self loops; this "
+                             f"conv has self_loop_type {self.self_loop_type}")
+        if blk.n_dst != n_dst:
+            raise ValueError(f"the block has {blk.n_dst} target rows, x_target {n_dst}")
+        # a_s over the capacity-sized source rows in one pass each way (regnn_attn_dots_fwd /
+        # _bwd: its second dot unused) instead of a product tensor and a reduction
+        a_s, _ = ops.attn_dots(x_src, self.att_src, self.att_src)            # :289
+        a_d = (x_dst * self.att_dst).sum(dim=-1)                             # :290
+        return ops.ns_gat(blk, a_s, a_d, tab, x_src, self.negative_slope)    # :298-312
+
     def forward(self, x, edge_index, edge_type=None, target_node_type=None,
                 return_weights=False):
         H, C = self.heads, self.out_channels
+        ns_block = getattr(edge_index, "is_ns_block", False)
         if isinstance(x, torch.Tensor):
             x_src = x_dst = self.lin_src(x).view(-1, H, C)
             n_dst = x.shape[0]
+        elif ns_block:
+            # the two projections bounded by the block's live rows where it carries the counts
+            # (NSTrainer's capacity-sized blocks: ~a quarter of the source rows are live at
+            # fan-out [25, 20]); the rows past them come out zero and nothing reads them
+            xs_in, xd_in = x
+            x_src = ops.linear(xs_in, self.lin_src.weight,
+                               live=getattr(edge_index, "live_src", None)).view(-1, H, C)
+            x_dst = ops.linear(xd_in, self.lin_dst.weight,
+                               live=getattr(edge_index, "live_rows", None)).view(-1, H, C)
+            n_dst = xd_in.shape[0]
         else:
             xs_in, xd_in = x
             x_src = self.lin_src(xs_in).view(-1, H, C)                       # :271-274
             x_dst = self.lin_dst(xd_in).view(-1, H, C)
             n_dst = xd_in.shape[0]
-        rg, pack = _block_of(x_src, x_dst, edge_index, edge_type, target_node_type,
-                             self.num_edge_types, self.self_loop_type)
-        assert rg.n_dst == n_dst
         tab = F.leaky_relu(self.relation_weight * self.scaling_factor)       # :294-295
-        a = self._attention(rg, pack, x_src, x_dst, tab)
-        out = ops.head_spmm(rg, a, x_src)                                    # propagate :312
+        if ns_block:
+            # a device-sampled block as the sampler left it (capacity-sized CSR, relation ids
+            # and self loops formed on the device): scores, the global-max softmax and the
+            # aggregation in ops.ns_gat, no exact sizes and no RelGraph rebuilt per step
+            out = self._block_attention(edge_index, x_src, x_dst, tab, n_dst, return_weights)
+        else:
+            rg, pack = _block_of(x_src, x_dst, edge_index, edge_type, target_node_type,
+                                 self.num_edge_types, self.self_loop_type)
+            assert rg.n_dst == n_dst
+            a = self._attention(rg, pack, x_src, x_dst, tab)
+            out = ops.head_spmm(rg, a, x_src)                                # propagate :312
         out = out.reshape(-1, H * C) if self.concat else out.mean(dim=1)     # :314-317
         out = out + self.bias                                                # :319
         if self.residual:
@@ -274,6 +309,11 @@ class REGATv2Conv(REGATConv):
 
     def _reset_att(self):
         init.xavier_uniform_(self.att)
+
+    def _block_attention(self, blk, x_src, x_dst, tab, n_dst, return_weights):
+        raise NotImplementedError("REGATv2Conv does not run on device-sampled blocks (ops.ns_gat "
+                                  "covers REGATConv's scores only): pass the exact-size "
+                                  "edge_index / edge_type adjs")
 
     def _attention(self, rg, pack, x_src, x_dst, tab):
         s = ops.gatv2_scores(rg, x_src, x_dst, self.att, self.negative_slope)  # :399-404
@@ -589,7 +629,12 @@ class REGNN(torch.nn.Module):
                 x = self.convs[i].forward_act(x, x_target, blk, ep[0], ep[1], i,
                                               tab=None if tabs is None else tabs[i])
                 continue                       # (relu and dropout applied in the epilogue)
-            if blk is not None and self.model == 'regcn' and self.self_loop_type == 2:
+            # (regat: REGATConv's attention over the block, ops.ns_gat -- only where the adj IS
+            # the block, NSTrainer(device_blocks=True); a PyG-style Adj carrying one keeps the
+            # exact-size path)
+            if (blk is not None and self.self_loop_type == 2 and
+                    (self.model == 'regcn' or
+                     (self.model == 'regat' and blk is edge_index))):
                 x = self.convs[i]((x, x_target), blk)          # relation ids formed on device
                 x = F.relu(x)
                 x = F.dropout(x, p=self.dropout, training=self.training)

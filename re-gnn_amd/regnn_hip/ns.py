@@ -466,6 +466,34 @@ def fused_unsupported(model, x_dict):
     return None
 
 
+def gat_blocks_unsupported(model, x_dict):
+    """why NSTrainer(device_blocks=True) cannot train this model on the sampler's capacity-sized
+    blocks (None: it can). Covered: mag.REGNN 'regat' (REGATConv over ops.ns_gat) with
+    self_loop_type 2 (the self loops the sampler writes), use_norm 'ln' or none, fp32 tables,
+    1..16 heads and a head width that is a multiple of 4 in [4, 512]."""
+    kind = getattr(model, "model", None)
+    if kind == "regatv2":
+        return ("regatv2: GATv2 scores have no device-block operator (ops.ns_gat covers "
+                "REGATConv only); it stays on the exact-size path")
+    if kind != "regat":
+        return f"model {kind!r} is neither 'regcn' nor 'regat'"
+    if getattr(model, "self_loop_type", None) != 2:
+        return (f"self_loop_type {getattr(model, 'self_loop_type', None)}: the sampler's blocks "
+                "carry self_loop_type 2's self loops (relation num_edge_types + node type)")
+    for c in model.convs:
+        if c.use_norm == "bn":
+            return ("use_norm 'bn': batch statistics over the capacity-sized rows would include "
+                    "the padded ones")
+        if c.use_norm not in ("ln", "non", None):
+            return f"use_norm {c.use_norm!r}"
+        if not (1 <= c.heads <= 16 and c.out_channels % 4 == 0 and 4 <= c.out_channels <= 512):
+            return (f"{c.heads} heads x {c.out_channels}: ops.ns_gat takes 1..16 heads and a "
+                    "head width that is a multiple of 4 in [4, 512]")
+    if any(torch.is_tensor(x) and x.dtype != torch.float32 for x in x_dict.values()):
+        return "the attention path reads fp32 input tables (no bf16 tables for 'regat')"
+    return None
+
+
 def fused_bf16_unsupported(model, sampler, x_dict):
     """why the fused step cannot read these bf16 input tables over this sampler's blocks (None: it
     can, or the tables are fp32). bf16 rows are read by the sampler's sums launch alone
@@ -1142,7 +1170,11 @@ class NSTrainer:
 
     def __init__(self, model, opt, rg, sizes, batch_size, train_idx, x_dict, edge_type,
                  node_type, local_node_idx, y_global, num_edge_types, seed=0, rank=0, world=1,
-                 shuffle=True, engine="auto", adam=None, pipeline=True):
+                 shuffle=True, engine="auto", adam=None, pipeline=True, device_blocks=False):
+        """device_blocks: also hand mag 'regat' models the capacity-sized device blocks
+        (REGATConv over ops.ns_gat: no host sync, pipelined, capturable) instead of the
+        exact-size adjs; raises ValueError where the blocks do not cover the model
+        (gat_blocks_unsupported). 'regcn' / self_loop_type 2 is on the blocks either way."""
         self.model, self.opt = model, opt
         dev = rg.device
         self.device, self.rank, self.world = dev, int(rank), int(world)
@@ -1156,10 +1188,22 @@ class NSTrainer:
         self.edge_type = torch.as_tensor(edge_type).to(dev, torch.int64)
         self.y_flat = y_global.reshape(-1).to(dev, torch.int64)
         # the module path hands 'regcn' / self_loop_type 2 the capacity-sized device blocks (no
-        # host sync: capturable); every other REGNN conv (regat, regatv2, other self-loop types)
-        # gets the PyG-style exact-size adjs and edge types (one host sync per step)
+        # host sync: capturable); every other REGNN conv (regat unless device_blocks, regatv2,
+        # other self-loop types) gets the PyG-style exact-size adjs and edge types (one host sync
+        # per step)
         self._blocks_ok = (getattr(model, "model", None) == "regcn" and
                            getattr(model, "self_loop_type", None) == 2)
+        # device_blocks: 'regat' too (mag.REGATConv reads the CSR blocks through ops.ns_gat);
+        # refused with a reason where the blocks do not apply (never a silent fall-back)
+        self._gat_blocks = False
+        if device_blocks and not self._blocks_ok:
+            why_not = gat_blocks_unsupported(model, x_dict)
+            if why_not is not None:
+                raise ValueError(f"device_blocks=True does not cover this model: {why_not}")
+            if engine == "fused":
+                raise ValueError("device_blocks=True: 'regat' runs on the module path, not the "
+                                 "fused step")
+            self._blocks_ok = self._gat_blocks = True
         self.params = [p for p in model.parameters() if p.requires_grad]
         # every parameter starts on a 16-byte boundary of the flat buckets (the fused step's
         # finalize sums and steps 4 aligned elements per thread); the pad elements stay zero.
@@ -1241,8 +1285,11 @@ class NSTrainer:
         # the sampling lookahead (fused engine: default_ahead; the module path: MODULE_AHEAD)
         self.ahead = 1
         if self.pipelined:
+            # 'regat' on device blocks: lookahead 1 whatever MODULE_AHEAD says (two slots,
+            # one-step graphs only: every captured graph keeps a private pool of activations,
+            # 573 MB per [cap_src, 512] tensor at 8 heads x 64, batch 512, fan-out [25, 20])
             self.ahead = max(1, int(default_ahead(self.world) if self.fused is not None
-                                    else MODULE_AHEAD["n"]))
+                                    else 1 if self._gat_blocks else MODULE_AHEAD["n"]))
         # parallel sampler lanes (lookahead groups): slot s samples on lane s mod L with that
         # lane's own dedup tables, so L batches of a group sample at the same time on L streams
         self.lanes = (max(1, int(SAMPLER_LANES["n"])) if self.pipelined and self.fused is not None
@@ -1312,6 +1359,12 @@ class NSTrainer:
             self._module_pre_sums(s, last)
         for h, blk in enumerate(s.blocks):
             blk.live_rows = s.sizes[h:h + 1]      # the block's live target rows (device count)
+        if self._gat_blocks:
+            # ops.ns_gat reads every hop in the CSR layout and differentiates by atomics
+            # (regnn_ns_gat_bwd form (b)): no strided hop, no transposed index, no input sums
+            for h, blk in enumerate(s.blocks):
+                blk.live_src = s.sizes[h + 1:h + 2]   # its live source rows (REGATConv's GEMMs)
+            return
         if s.blocks[0].csr_idx.numel() <= 32768:
             _, cptr, cent, clong = s.csc[0] or s.enable_csc(0)
             b0 = s.blocks[0]
@@ -1830,7 +1883,7 @@ class NSTrainer:
                         with _capturing(g):
                             self._ahead_group(start, m, in_graph)
                         self.graph_groups[(m, start)] = g
-            elif fold_opt:
+            elif fold_opt and not self._gat_blocks:
                 # 2 and 4 steps back to back in one graph (the slot parity returns to 0):
                 # run_steps replays them for runs of steps, one graph boundary (~9 us of queue
                 # idle between replays) per group instead of per step

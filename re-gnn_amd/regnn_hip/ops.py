@@ -677,6 +677,94 @@ def ns_spmm(blk, x, tab=None, bias=None):
     return _NsSpmm.apply(x, tab, bias, blk)
 
 
+NS_GAT_WORK_FLOATS = 2048        # include/regnn_hip.h REGNN_NS_GAT_WORK_FLOATS
+# workgroups (= relation-slab rows) of regnn_ns_gat_bwd with a relation table: a wave per row,
+# four per workgroup, at most this many
+NS_GAT_BWD_ROWS = {"n": int(os.environ.get("REGNN_NS_GAT_BWD_ROWS", "1024"))}
+
+
+def ns_gat_bytes(E, n_dst, H, C, kind):
+    """algorithmic HBM bytes of the sampled-block attention: per entry its id, relation, a and
+    the gathered ft row (the backward: the row read for ga and the atomic row into g_ft), per
+    target its ptr, er and out / gy row."""
+    if kind == "fwd":
+        return E * (5 + 12 * H + 4 * H * C) + n_dst * (4 + 4 * H + 4 * H * C)
+    return E * (5 + 16 * H + 8 * H * C) + n_dst * (4 + 8 * H + 4 * H * C)
+
+
+class _NsGat(torch.autograd.Function):
+    """(out, a) of regnn_ns_gat_fwd over a device-sampled block in the CSR layout; backward
+    regnn_ns_gat_bwd (+ regnn_rel_reduce for the relation table). a is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, el, er, tab, ft, blk, slope):
+        for name, t in (("el", el), ("er", er), ("tab", tab), ("ft", ft)):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError(f"ns_gat: {name} is {t.dtype}; the sampled-block attention runs "
+                                "on fp32")
+        if getattr(blk, "strided_rows", None) is not None:
+            raise ValueError("ns_gat reads the CSR layout; this block was sampled in the "
+                             "fixed-stride layout (strided_rows)")
+        if ft.dim() != 3 or el.dim() != 2 or er.dim() != 2:
+            raise ValueError("ns_gat: ft [n, H, C], el [n, H], er [n_dst, H]")
+        H, C = int(ft.shape[1]), int(ft.shape[2])
+        if (el.shape[0] != ft.shape[0] or el.shape[1] != H or tuple(er.shape) != (blk.n_dst, H) or
+                (tab is not None and (tab.dim() != 2 or tab.shape[1] != H))):
+            raise ValueError(f"ns_gat: el {tuple(el.shape)}, er {tuple(er.shape)}, ft "
+                             f"{tuple(ft.shape)} do not fit a block of {blk.n_dst} targets")
+        el, er, ft = el.contiguous(), er.contiguous(), ft.contiguous()
+        t = None if tab is None else tab.detach().contiguous()
+        n_src = min(int(ft.shape[0]), blk.n_src)
+        a = torch.empty(blk.csr_idx.numel(), H, dtype=torch.float32, device=ft.device)
+        out = torch.empty(blk.n_dst, H, C, dtype=torch.float32, device=ft.device)
+        work = torch.empty(NS_GAT_WORK_FLOATS, dtype=torch.float32, device=ft.device)
+        with timed("ns_gat_fwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "fwd")):
+            L.call("regnn_ns_gat_fwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+                   L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
+                   L.ptr(ft), float(slope), blk.n_dst, n_src, H, C, L.ptr(a), L.ptr(out),
+                   L.ptr(work), L.stream())
+        ctx.blk, ctx.slope, ctx.n_src = blk, float(slope), n_src
+        ctx.tab_shape = None if tab is None else tab.shape
+        ctx.save_for_backward(el, er, t, ft, a)
+        ctx.mark_non_differentiable(a)
+        return out, a
+
+    @staticmethod
+    def backward(ctx, gy, _ga):
+        el, er, t, ft, a = ctx.saved_tensors
+        blk = ctx.blk
+        H, C = int(ft.shape[1]), int(ft.shape[2])
+        gy = gy.contiguous().float()
+        g_ft, g_el = torch.zeros_like(ft), torch.zeros_like(el)      # the atomics' targets
+        g_er = torch.empty_like(er)
+        n_rel = int(t.shape[0]) if t is not None else 0
+        slab, rows = None, 0
+        if t is not None and ctx.needs_input_grad[2]:
+            rows = max(1, min(NS_GAT_BWD_ROWS["n"], NS_GAT_WORK_FLOATS, -(-blk.n_dst // 4)))
+            slab = torch.empty(rows, n_rel * H, dtype=torch.float32, device=ft.device)
+        with timed("ns_gat_bwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "bwd")):
+            L.call("regnn_ns_gat_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+                   L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
+                   L.ptr(ft), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C, n_rel,
+                   L.ptr(g_ft), L.ptr(g_el), L.ptr(g_er), L.ptr(slab), rows, L.stream())
+        g_tab = _reduce(slab, n_rel * H).view(ctx.tab_shape) if slab is not None else None
+        return g_el, g_er, g_tab, g_ft, None, None
+
+
+def ns_gat(blk, el, er, tab, ft, slope=0.2, return_attn=False):
+    """mag REGATConv's attention and aggregation over a device-sampled block as the sampler
+    leaves it (regnn_hip.ns.NSBlock in the CSR layout, capacity-sized, no host size):
+    out[v,h,:] = sum_e a[e,h] ft[idx_e,h,:], a = the ogbn-mag softmax (one global maximum,
+    + 1e-16, mag/utils.py:45-57) of LeakyReLU(el[idx_e] + er[v] + tab[rel_e], slope)
+    (mag/regnn_layers.py:253-273). el / ft hold the block's source rows (>= blk.n_src rows; rows
+    past the sampled ones unread, their gradients zero), er the blk.n_dst target rows; rows of
+    out past the batch's live targets are zeros. The backward is gat_attention(global_max=True)'s
+    (the maximum a constant); its per-source sums use float atomics (regnn_ns_gat_bwd).
+    return_attn: also a [blk capacity entries, H] (no gradient)."""
+    out, a = _NsGat.apply(el, er, tab, ft, blk, slope)
+    return (out, a) if return_attn else out
+
+
 
 class _NsTypedAgg(torch.autograd.Function):
     """S[v, t] = sum_{e in v, type(src) = t} tab[rel_e] x_src (raw input rows read through n_id /
@@ -1895,27 +1983,32 @@ class _MMx6(torch.autograd.Function):
 
 class _LinearX6(torch.autograd.Function):
     """x @ w^T + bias (nn.Linear: w [N, K]) with regnn_gemm_x6 forward and backward: gx = g w,
-    gw = g^T x (w's own layout), gbias = the column sums of g."""
+    gw = g^T x (w's own layout), gbias = the column sums of g. live (a one-element int32 device
+    tensor, or None): x's live rows -- a capacity-sized sampled block's rows past it feed nothing,
+    so the three products skip them: the output's rows there are the bias (zeros without one),
+    and the incoming gradient's rows there must be zero (gx's are written as zeros)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias):
+    def forward(ctx, x, w, bias, live=None):
         if bias is None:
-            out = gemm_x6(x, w, trans_b=True)
+            out = gemm_x6(x, w, trans_b=True, m_live=live)
         else:
             out = bias.expand(x.shape[0], w.shape[0]).contiguous()
-            gemm_x6(x, w, trans_b=True, out=out, beta=1.0)
+            gemm_x6(x, w, trans_b=True, out=out, beta=1.0, m_live=live)
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
+        ctx.live = live
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         g = g.contiguous()
-        gx = gemm_x6(g, w) if ctx.needs_input_grad[0] else None
-        gw = gemm_x6(g, x, trans_a=True) if ctx.needs_input_grad[1] else None
+        live = ctx.live
+        gx = gemm_x6(g, w, m_live=live) if ctx.needs_input_grad[0] else None
+        gw = gemm_x6(g, x, trans_a=True, k_live=live) if ctx.needs_input_grad[1] else None
         gb = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        return gx, gw, gb
+        return gx, gw, gb, None
 
 
 class _Copy2d(ctypes.Structure):
@@ -1946,11 +2039,14 @@ def copy_many(dst, src):
         L.call("regnn_copy2d_many", ctypes.addressof(arr), len(descs), L.stream())
 
 
-def linear(x, w, bias=None):
-    """nn.functional.linear on regnn_gemm_x6 when the operands allow it (else torch)."""
+def linear(x, w, bias=None, live=None):
+    """nn.functional.linear on regnn_gemm_x6 when the operands allow it (else torch). live: a
+    one-element int32 device tensor with x's live rows (_LinearX6; torch's product ignores it)."""
     if (GEMM_X6["mode"] != "off" and x.dim() == 2 and gemm_x6_ok(x, w) and
             (bias is None or (bias.is_cuda and bias.dtype == torch.float32 and bias.dim() == 1))):
-        return _LinearX6.apply(x, w, bias)
+        live_ok = (live is not None and live.is_cuda and live.dtype == torch.int32 and
+                   live.numel() == 1 and LIVE_ROWS["mode"] != "off")
+        return _LinearX6.apply(x, w, bias, live if live_ok else None)
     return torch.nn.functional.linear(x, w, bias)
 
 
