@@ -833,6 +833,56 @@ int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
                      int32_t C, int32_t n_rel, float* g_ft, float* g_el, float* g_er, float* slab,
                      int32_t slab_rows, hipStream_t stream);
 
+/* Forward-only attention of the mag REGATConv / REGATv2Conv layers for the layer-wise
+ * full-neighbour inference (mag/regnn_ns.py:348-369), in two calls.
+ *
+ * regnn_mag_attn_fwd: score + online softmax + per-head aggregation over the CSR (ptr, idx, rel)
+ * in one pass, no [E, H] tensor written. Per row v and head h, over the row's entries e (u = idx_e):
+ *   kind REGNN_ATTN_GAT, el given:  s_e = LeakyReLU_slope(el[u,h] + er[v,h] + tab[rel_e,h])
+ *   kind REGNN_ATTN_GAT, el NULL:   the same with el[u,h] = <x[u,h,:], att[h,:]> re-formed from the
+ *                                   gathered row in regnn_attn_dots_fwd's vector order (att = attn_l)
+ *   kind REGNN_ATTN_GATV2:          s_e = sum_d att[h,d] LeakyReLU_slope(x[u,h,d] + xd[v,h,d])
+ *                                         + tab[rel_e,h]          (no outer activation; el, er unread)
+ *   rmax[v,h] = max_e s_e,   rsum[v,h] = sum_e exp(s_e - rmax),
+ *   acc[v,h,:] = sum_e exp(s_e - rmax) x[u,h,:]                   (NOT divided by rsum)
+ * A row without entries gives acc = 0, rmax = -inf, rsum = 0. GATv2 forms its score from the row
+ * x[u] it aggregates (in the mag layers lin_dst is lin_src and the message is x_src): one random
+ * access per entry; xd [n_seg, H*D] are the rows' own slices (xd = x rows of the destinations).
+ * tab [n_rel, H] may be NULL (no relation term; rel then unread). x [>= n_src, H*D], acc
+ * [n_seg, H*D], all fp32, rows 16-byte aligned. Rows longer than the plan's split run as chunks
+ * into partial rows [acc | max | sum] (partial width H*D + 2H) combined by the plan's fixed-order
+ * tree, as regnn_gat_fused_fwd's; sums run in entry / chunk / tree order without atomics, so a
+ * second call returns the same bits.
+ * D % 4 == 0 and 1 <= H with H*D <= REGNN_MAG_ATTN_MAX_WIDTH (the lane layout: 64 lanes x 8
+ * 16-byte vectors); the el-NULL and GATv2 kinds also need D / 4 a power of two <= 64 (the head's
+ * lanes reduce by an xor butterfly); otherwise REGNN_EUNSUPPORTED. A NULL required pointer, tab
+ * without rel or an unknown kind: REGNN_EINVAL. Both before any launch.
+ *
+ * regnn_mag_attn_epilogue: the ogbn-mag softmax (mag/utils.py:45-57: ONE maximum gmax over every
+ * entry and head, + eps in the denominator) from those per-row quantities, then the layer's tail
+ * (concat = True), one launch over n rows of H*D:
+ *   y[v, h D + d] = acc[v,h,d] / (rsum[v,h] + eps exp(gmax - rmax[v,h])) + bias + res[v,:]
+ *   then LayerNorm(ln_weight, ln_bias, ln_eps) if flags & 1, then relu if flags & 2.
+ * In exact arithmetic exp(s - gmax) / (sum exp(s' - gmax) + eps) = exp(s - m) / (S + eps
+ * exp(gmax - m)) for any m; the quotient is formed from rmax and rsum separately (never from
+ * rmax + log rsum, whose rounding alone is 1e-6 relative at |score| = 16), the denominator in
+ * fp64. gmax is one float in device memory (the caller's max over rmax, MAX-reduced over ranks).
+ * rsum = 0 gives a zero attention term, and so does a gmax - rmax that overflows the exponential
+ * (never NaN). bias, res, ln_weight, ln_bias may be NULL. y may not alias acc or res.
+ * Added without an ABI bump (the version stays 51), as regnn_ns_gat_*: two new symbols only. */
+enum { REGNN_ATTN_GAT = 0, REGNN_ATTN_GATV2 = 1 };
+#define REGNN_MAG_ATTN_MAX_WIDTH 2048
+int regnn_mag_attn_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                       const float* tab, int32_t kind, const float* el, const float* er,
+                       const float* att, const float* x, const float* xd, float* acc,
+                       float* rmax, float* rsum, int64_t n_seg, int32_t H, int32_t D, float slope,
+                       const regnn_seg_plan* plan, hipStream_t stream);
+int regnn_mag_attn_epilogue(const float* acc, const float* rmax, const float* rsum,
+                            const float* gmax, float eps, const float* bias, const float* res,
+                            const float* ln_weight, const float* ln_bias, float ln_eps,
+                            int32_t flags, int64_t n, int32_t H, int32_t D, float* y,
+                            hipStream_t stream);
+
 /* Typed aggregation of raw input rows over a sampled block (layer 0 of the NS REGNN at any hidden
  * width; mag/regnn_ns.py:300-326 group_input + mag/regnn_layers.py:101-148, replacing the
  * reference's per-type Linear over every sampled node and x_src @ W before propagate):

@@ -7,10 +7,9 @@
 //  * the softmax / LeakyReLU / u_add_v backward with deterministic relation-bias slabs.
 #include "regnn_common.h"
 #include "re_segplan.h"
+#include "re_gat_fused.h"
 
 namespace regnn {
-
-__device__ __forceinline__ float lrelu(float x, float slope) { return x > 0.f ? x : x * slope; }
 
 __global__ void __launch_bounds__(kBlock)
 gat_softmax_fwd_generic(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
@@ -496,185 +495,7 @@ inline int gat_log2(int H) {    // log2(H) if H is a power of two <= kGatGroup, 
     return -1;
 }
 
-// ---- fused score + edge softmax + weighted SpMM (layer/REGATConv.py:80-92) ---------------
-// One pass per destination v: for each in-edge u -> v and head h the score
-// e = LeakyReLU(el[u,h] + er[v,h] + ee[rel,h]) enters an online softmax (running max m, sum s,
-// accumulator rescaled when the max grows) while the same lanes gather x[u,h,:]:
-//   out[v,h,:] = sum_e exp(e - m) x[u,h,:] / s,   lse[v,h] = m + log s.
-// Every lane of a head carries its own copy of (m, s) (identical: the same scores), so no
-// cross-lane reduction is needed; a[e,h] is never written (the backward re-forms it from lse).
-// Lanes / vectors as spmm_heads_kernel; edge ids loaded cooperatively, UN rows in flight.
-struct GatFusedArgs {
-    const int32_t* ptr;
-    const int32_t* idx;
-    const uint8_t* rel;
-    const float* ee;
-    const float* el;
-    const float* er;
-    const void* x;
-    void* out;
-    float* lse;
-    const float* al;    // attn_l [H, D] (ELX kernels: el re-formed from the gathered row)
-    int64_t n_seg;
-    int H, D;
-    float slope;
-};
-
-// el[u,h] as attn_dots_fwd_vec forms it: lane l of the head's D/4 lanes takes x[u,h,4l..4l+3]
-// (an fmaf chain from 0), then an xor butterfly over the D/4 lanes (every lane ends with the same
-// sum). The ELX forward forms it from the row it already holds, so each edge makes one random
-// access (the row) instead of two (the row and el[u], 32 B of another array): bitwise the el the
-// backward re-forms the attention from.
-__device__ __forceinline__ float head_dot4(const float (&v)[4], const float (&a)[4], int dl) {
-    float d = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) d = fmaf(v[t], a[t], d);
-    for (int o = dl >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-    return d;
-}
-
-// attn_dots_fwd in the order head_dot4 uses: D % 4 == 0 and D / 4 a power of two <= 64
-inline bool attn_dots_vec_ok(int D) {
-    const int dl = D / 4;
-    return D > 0 && D % 4 == 0 && dl <= 64 && (dl & (dl - 1)) == 0;
-}
-
-// CH: the units are the chunks of long segments (partial rows [acc | max | sum], unnormalised);
-// otherwise the segments, long ones skipped.
-template <typename T, int LPR, int NV, bool CH, bool ELX>
-__global__ void __launch_bounds__(kBlock) gat_fused_fwd_kernel(GatFusedArgs p, LongPlan P) {
-    constexpr int EV = Vec<T>::N;
-    static_assert(!ELX || EV == 4, "ELX: fp32 rows");
-#ifdef REGNN_GATF_UN
-    constexpr int UN = NV <= 2 ? REGNN_GATF_UN : (NV <= 4 ? 4 : 2);
-#else
-    constexpr int UN = NV <= 4 ? 4 : 2;    // 8 rows for NV <= 2: 25.5 / 18.2 ms against 24.7 / 17.2
-#endif
-    constexpr int GPB = kBlock / LPR;
-    const int tid = threadIdx.x, lane = tid & (LPR - 1);
-    const int F = p.H * p.D;
-    const T* __restrict__ src = static_cast<const T*>(p.x);
-    const int64_t n_units = CH ? P.n_chunk : p.n_seg;
-    for (int64_t unit = (int64_t)blockIdx.x * GPB + tid / LPR; unit < n_units;
-         unit += (int64_t)gridDim.x * GPB) {
-        int64_t seg;
-        int beg, end;
-        if (CH) {
-            chunk_range(P, p.ptr, unit, seg, beg, end);
-        } else {
-            seg = unit;
-            beg = p.ptr[seg];
-            end = p.ptr[seg + 1];
-            if (end - beg > P.split) continue;         // a long segment: its chunks
-        }
-        float acc[NV][EV] = {};
-        float m[NV], s[NV], erv[NV];
-        float alv[ELX ? NV : 1][4];
-        int head[NV];
-#pragma unroll
-        for (int q = 0; q < NV; ++q) {
-            const int o = (q * LPR + lane) * EV;
-            head[q] = o < F ? o / p.D : 0;
-            erv[q] = p.er[seg * p.H + head[q]];
-            m[q] = -INFINITY;
-            s[q] = 0.f;
-            if constexpr (ELX) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) alv[q][t] = o < F ? p.al[o + t] : 0.f;
-            }
-        }
-        for (int e0 = beg; e0 < end; e0 += LPR) {
-            const int e = e0 + lane;
-            int j = 0, r = 0;
-            if (e < end) {
-                j = p.idx[e];
-                r = p.ee ? int(p.rel[e]) : 0;
-            }
-            const int cnt = min(LPR, end - e0);
-            for (int k0 = 0; k0 < cnt; k0 += UN) {
-                float v[UN][NV][EV];
-                float sc[UN][NV];
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int kk = min(k0 + u, cnt - 1);
-                    const int jj = __shfl(j, kk, LPR);
-                    const int rr = __shfl(r, kk, LPR);
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) {
-                        const int o = (q * LPR + lane) * EV;
-                        if (o < F) {
-                            Vec<T>::load(src + (int64_t)jj * F + o, v[u][q]);
-                            if constexpr (ELX) {       // the relation bias; el once the row is in
-                                sc[u][q] = p.ee ? p.ee[rr * p.H + head[q]] : 0.f;
-                            } else {
-                                float z = p.el[(int64_t)jj * p.H + head[q]] + erv[q];
-                                if (p.ee) z += p.ee[rr * p.H + head[q]];
-                                sc[u][q] = lrelu(z, p.slope);
-                            }
-                        } else {
-#pragma unroll
-                            for (int t = 0; t < EV; ++t) v[u][q][t] = 0.f;
-                            sc[u][q] = 0.f;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    if (k0 + u >= cnt) break;
-                    if constexpr (ELX) {
-#pragma unroll
-                        for (int q = 0; q < NV; ++q) {
-                            float z = head_dot4(v[u][q], alv[q], p.D >> 2) + erv[q];
-                            if (p.ee) z += sc[u][q];
-                            sc[u][q] = lrelu(z, p.slope);
-                        }
-                    }
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) {
-                        const float d = sc[u][q] - m[q];
-                        const bool grow = d > 0.f;                   // new running max
-                        const float ex = __expf(grow ? -d : d);
-                        const float sa = grow ? ex : 1.f, sv = grow ? 1.f : ex;
-#pragma unroll
-                        for (int t = 0; t < EV; ++t) acc[q][t] = fmaf(acc[q][t], sa, sv * v[u][q][t]);
-                        s[q] = fmaf(s[q], sa, sv);
-                        m[q] = grow ? sc[u][q] : m[q];
-                    }
-                }
-            }
-        }
-        if (CH) {
-            float* __restrict__ pr = P.part + unit * (F + 2 * p.H);
-#pragma unroll
-            for (int q = 0; q < NV; ++q) {
-                const int o = (q * LPR + lane) * EV;
-                if (o < F) {
-#pragma unroll
-                    for (int t = 0; t < EV; ++t) pr[o + t] = acc[q][t];
-                    if (o % p.D == 0) {
-                        pr[F + head[q]] = m[q];
-                        pr[F + p.H + head[q]] = s[q];
-                    }
-                }
-            }
-            continue;
-        }
-        T* __restrict__ out = static_cast<T*>(p.out) + seg * F;
-#pragma unroll
-        for (int q = 0; q < NV; ++q) {
-            const int o = (q * LPR + lane) * EV;
-            if (o < F) {
-                const float inv = s[q] > 0.f ? 1.f / s[q] : 0.f;
-                float w[EV];
-#pragma unroll
-                for (int t = 0; t < EV; ++t) w[t] = acc[q][t] * inv;
-                Vec<T>::store(out + o, w);
-                if (o % p.D == 0)
-                    p.lse[seg * p.H + head[q]] = s[q] > 0.f ? m[q] + __logf(s[q]) : -INFINITY;
-            }
-        }
-    }
-}
+// ---- fused score + edge softmax + weighted SpMM: gat_fused_fwd_kernel, re_gat_fused.h --------
 
 // a[e,h] = exp(LeakyReLU(el[u,h] + er[v,h] + ee[rel,h]) - lse[v,h]) in CSR edge order (the
 // attention the fused forward did not store; its backward needs it). Group layout of
@@ -716,6 +537,7 @@ gat_attn_lse_group(const int32_t* __restrict__ ptr, const int32_t* __restrict__ 
 template <typename T>
 int dispatch_gat_fused(GatFusedArgs p, const regnn_seg_plan* pl, hipStream_t stream) {
     constexpr int EV = Vec<T>::N;
+    constexpr int SCX = EV == 4 ? kScoreElx : kScoreEl;    // (the ELX form: fp32 rows only)
     const int F = p.H * p.D;
     if (p.D <= 0 || p.D % EV || p.H <= 0) return REGNN_EUNSUPPORTED;
     const int nvec = F / EV;
@@ -728,21 +550,21 @@ int dispatch_gat_fused(GatFusedArgs p, const regnn_seg_plan* pl, hipStream_t str
         const bool elx = std::is_same<T, float>::value && p.al && attn_dots_vec_ok(p.D) &&    \
                          p.D / 4 <= (LPR);                                                    \
         if (elx)                                                                              \
-            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, EV == 4>),            \
+            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, SCX, false>),         \
                                dim3(grid_for(p.n_seg, kBlock / (LPR))), dim3(kBlock), 0, stream, \
                                p, P);                                                         \
         else                                                                                  \
-            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, false>),              \
+            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, kScoreEl, false>),    \
                                dim3(grid_for(p.n_seg, kBlock / (LPR))), dim3(kBlock), 0, stream, \
                                p, P);                                                         \
         REGNN_LAUNCH_CHECK();                                                                 \
         if (P.n_chunk > 0) {                                                                  \
             if (elx)                                                                          \
-                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, EV == 4>),         \
+                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, SCX, false>),      \
                                    dim3(grid_for(P.n_chunk, kBlock / (LPR))), dim3(kBlock), 0, \
                                    stream, p, P);                                             \
             else                                                                              \
-                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, false>),           \
+                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, kScoreEl, false>), \
                                    dim3(grid_for(P.n_chunk, kBlock / (LPR))), dim3(kBlock), 0, \
                                    stream, p, P);                                             \
             const int64_t base = run_tree(pl, 1, F + 2 * p.H, F, p.H, p.D, stream);           \

@@ -17,6 +17,18 @@ the rows it owns. The aggregation is the same HIP SpMM as training (relation tab
 and bias fused; hub rows through the chunk + tree path). Each block holds the rank's CSR row
 range with the target self loops appended last in every row, as the sampled blocks do
 (mag/regnn_layers.py:90-96), so a rank's output rows equal the reference's batch outputs.
+
+The attention models ('regat', 'regatv2'; mag/regnn_layers.py:253-325, 394-436) exchange the
+projected rows xs = x @ lin_src.weight^T the same way; a layer is then
+
+    acc, rmax, rsum = fused scores + online softmax + per-head aggregate   (regnn_mag_attn_fwd)
+    gmax            = max over ranks of max rmax        (one float, MAX all-reduce)
+    out_r           = acc / (rsum + 1e-16 exp(gmax - rmax)) + bias (+ xs_r), LayerNorm, relu
+                                                        (regnn_mag_attn_epilogue)
+
+The softmax of mag/utils.py:45-57 subtracts ONE maximum over every entry and head of a batch;
+here it is the maximum over the whole graph: the reference with a single loader batch. How the
+loader batches moves only the 1e-16 term, and the result does not depend on the world size.
 """
 import torch
 import torch.distributed as dist
@@ -113,8 +125,9 @@ class ShardedInference:
 
     def __init__(self, model, rg, edge_type, node_type, local_node_idx, rank=0, world=1,
                  bounds=None):
-        if getattr(model, "model", "regcn") != "regcn":
-            raise NotImplementedError("sharded full-neighbour inference covers the REGCN model")
+        self.kind = getattr(model, "model", "regcn")
+        if self.kind not in ("regcn", "regat", "regatv2"):
+            raise NotImplementedError(f"sharded full-neighbour inference: model {self.kind!r}")
         if model.self_loop_type != 2:
             raise NotImplementedError("full-neighbour inference is built for self_loop_type=2 "
                                       "(the mag/regnn_ns.py default)")
@@ -129,7 +142,10 @@ class ShardedInference:
 
     @torch.no_grad()
     def project(self, layer, x_loc):
-        return x_loc @ self.model.convs[layer].weight                      # :101-102
+        conv = self.model.convs[layer]
+        if self.kind != "regcn":
+            return x_loc @ conv.lin_src.weight.t()                         # :271-274
+        return x_loc @ conv.weight                                         # :101-102
 
     @torch.no_grad()
     def input(self, x_dict, layer=0):
@@ -169,10 +185,14 @@ class ShardedInference:
         return x, self.project(layer, x)
 
     @torch.no_grad()
-    def aggregate(self, layer, xs_all, xs_loc):
+    def aggregate(self, layer, xs_all, xs_loc, group=None):
         """one HIP pass: mean aggregation with the relation table and bias, + residual,
-        LayerNorm and relu fused in the epilogue (regnn_spmm_fwd_fused)."""
+        LayerNorm and relu fused in the epilogue (regnn_spmm_fwd_fused). The attention models:
+        attention_scores, the MAX all-reduce of the one global maximum, attention_finish."""
         conv = self.model.convs[layer]
+        if self.kind != "regcn":
+            return self.attention_finish(layer, self.attention_scores(layer, xs_all, xs_loc),
+                                         xs_loc, group=group)
         tab = F.leaky_relu(conv.relation_weight * conv.scaling_factor)     # :110-111
         blk = self.block
         res = xs_loc if conv.residual else None                            # x_target @ W
@@ -186,6 +206,43 @@ class ShardedInference:
             ln = (conv.norm.weight, conv.norm.bias, conv.norm.eps)
         return ops.re_spmm_fused(blk, xs_all, tab, blk.pack, post=blk.inv_in_count(),
                                  bias=conv.bias, residual=res, ln=ln, relu=True)
+
+    @torch.no_grad()
+    def attention_scores(self, layer, xs_all, xs_loc):
+        """first half of an attention layer over the own rows (ops.mag_attn_scores): scores,
+        online softmax and the unnormalised aggregate in one pass, and .gmax, this rank's
+        maximum score. The softmax of mag/utils.py:45-57 subtracts ONE maximum over every entry
+        and head of the batch; here the batch is the whole graph (the reference with one batch),
+        so the ranks' maxima are MAX-reduced before attention_finish."""
+        conv = self.model.convs[layer]
+        H, C = conv.heads, conv.out_channels
+        if not conv.concat:
+            raise NotImplementedError("full-neighbour inference of the attention models is built "
+                                      "for concat=True (what mag.REGNN constructs)")
+        tab = F.leaky_relu(conv.relation_weight * conv.scaling_factor)     # :294-295
+        kw = (dict(att=conv.att) if conv.v2 else
+              dict(att_src=conv.att_src, att_dst=conv.att_dst))
+        return ops.mag_attn_scores(self.block, xs_all.view(-1, H, C), xs_loc.view(-1, H, C),
+                                   "gatv2" if conv.v2 else "gat", tab, conv.negative_slope, **kw)
+
+    @torch.no_grad()
+    def attention_finish(self, layer, st, xs_loc, gmax=None, group=None):
+        """second half: the softmax with the global maximum (gmax given: a lockstep caller's
+        maximum over its ranks; else st.gmax MAX-reduced over the process group), bias,
+        residual, LayerNorm and relu in the epilogue launch (:319-325, regnn_ns.py:361-362)."""
+        conv = self.model.convs[layer]
+        if gmax is None:
+            gmax = st.gmax
+            if self.world > 1:
+                gmax = gmax.clone()
+                dist.all_reduce(gmax, op=dist.ReduceOp.MAX, group=group)
+        res = xs_loc if conv.residual else None                            # x_dst = lin_dst(x)
+        if conv.use_norm == 'bn':
+            return F.relu(conv.norm(st.finish(gmax, conv.bias, res)))
+        ln = None
+        if conv.use_norm == 'ln':
+            ln = (conv.norm.weight, conv.norm.bias, conv.norm.eps)
+        return st.finish(gmax, conv.bias, res, ln, relu=True)
 
     @torch.no_grad()
     def head(self, x_loc):
@@ -204,7 +261,7 @@ class ShardedInference:
         _, xs = self.input(x_dict, 0)
         for layer in range(L):
             xs_all = exchange_rows(xs, self.bounds, self.rank, self.world, group)
-            x = self.aggregate(layer, xs_all, xs)
+            x = self.aggregate(layer, xs_all, xs, group)
             del xs_all
             if layer + 1 < L:
                 xs = self.project(layer + 1, x)

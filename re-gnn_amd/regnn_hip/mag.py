@@ -333,7 +333,9 @@ REL_TABS = os.environ.get("REGNN_REL_TABS", "1") != "0"
 
 
 class REGNN(torch.nn.Module):
-    """mag/regnn_ns.py:216-369 for model 'regcn' (feats_type != 2)."""
+    """mag/regnn_ns.py:216-369 for the models 'regcn', 'regat' and 'regatv2' (feats_type 2: the
+    learned per-type embeddings): forward() over sampled batches, inference() /
+    inference_sharded() layer-wise over every in-edge, for all three models."""
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, scaling_factor,
                  dropout, num_feature_dict, num_edge_types, residual=False, no_re=False,
@@ -663,7 +665,11 @@ class REGNN(torch.nn.Module):
         sizes=[-1] over all nodes) or the global RelGraph itself. Its batches are row ranges of
         the full graph, so each layer runs as one full-graph aggregation with the layer input
         resident in HBM (regnn_hip/inference.py); ``inference_sharded`` splits the rows over
-        data-parallel ranks."""
+        data-parallel ranks. All three models (self_loop_type 2): 'regcn' runs the fused mean
+        SpMM, 'regat' / 'regatv2' the forward-only fused attention (ops.mag_attn_scores +
+        the epilogue). The attention softmax subtracts ONE maximum over every entry and head
+        (mag/utils.py:45-57); here it is the maximum over the whole graph, i.e. the reference
+        with the loader's batch size >= N (another batching moves only the 1e-16 term)."""
         rg = getattr(subgraph_loader, "rg", subgraph_loader)
         sizes = getattr(subgraph_loader, "sizes", [-1])
         if list(sizes) != [-1]:
@@ -675,7 +681,9 @@ class REGNN(torch.nn.Module):
     def inference_sharded(self, x_dict, rg, edge_type, node_type, local_node_idx, rank, world,
                           gather="logits", group=None):
         """inference() with the destination rows split over ``world`` ranks and one all-gather
-        per layer (RCCL over xGMI); gather=None returns only this rank's rows."""
+        per layer (RCCL over xGMI); gather=None returns only this rank's rows. The attention
+        models add a MAX all-reduce of one float per layer (the softmax's global maximum), so the
+        result does not depend on the world size."""
         from .inference import ShardedInference
         return ShardedInference(self, rg, edge_type, node_type, local_node_idx, rank,
                                 world).run(x_dict, gather=gather, group=group)

@@ -1459,6 +1459,199 @@ def head_spmm(rg, a, ft):
 
 
 # ---------------------------------------------------------------------------------------------
+# Forward-only attention of the mag REGATConv / REGATv2Conv layers (full-neighbour inference).
+MAG_ATTN_MAX_WIDTH = 2048        # include/regnn_hip.h REGNN_MAG_ATTN_MAX_WIDTH
+# the form mag_attn_scores takes per kind: "fused" (regnn_mag_attn_fwd + _epilogue) or "chain"
+# (the existing operators: scores -> edge softmax -> per-head SpMM, the tail in torch).
+# Defaults by measurement (tools/attn_infer_time.py).
+MAG_ATTN_FORM = {"gat": os.environ.get("REGNN_MAG_ATTN_GAT", "fused"),
+                 "gatv2": os.environ.get("REGNN_MAG_ATTN_GATV2", "fused")}
+
+
+def _vec_dots_ok(D):
+    dl = D // 4
+    return D > 0 and D % 4 == 0 and dl <= 64 and dl & (dl - 1) == 0
+
+
+def mag_attn_fused_ok(kind, H, D, x=None):
+    """shapes regnn_mag_attn_fwd takes for mag_attn_scores' calls (fp32 rows)."""
+    if x is not None and x.dtype != torch.float32:
+        return False
+    if H < 1 or D < 4 or D % 4 or H * D > MAG_ATTN_MAX_WIDTH:
+        return False
+    return kind == "gat" or _vec_dots_ok(D)
+
+
+class MagAttn:
+    """The first half of one attention layer over a row block: whatever the second half needs,
+    and .gmax, a 1-element tensor with the maximum score over the block's entries and heads
+    (-inf: none). finish() is the second half: the ogbn-mag softmax with ONE maximum (gmax:
+    .gmax, or the caller's -- the MAX over every rank's), the aggregate, bias / residual /
+    LayerNorm / relu -> y [n_dst, H * D]."""
+
+    def __init__(self, form, blk, H, D):
+        self.form, self.blk, self.H, self.D = form, blk, H, D
+
+    @torch.no_grad()
+    def finish(self, gmax=None, bias=None, residual=None, ln=None, relu=False, eps=1e-16):
+        gmax = self.gmax if gmax is None else gmax.reshape(1).float()
+        if self.form == "fused":
+            return mag_attn_epilogue(self.acc, self.rmax, self.rsum, gmax, bias, residual, ln,
+                                     relu, eps)
+        blk, H, D = self.blk, self.H, self.D
+        a = torch.empty_like(self.s)
+        gp = _GatPlan(getattr(blk, "csr_plan", None), 2 * H, a.device)
+        rel, t = self.rel_tab
+        with timed("edge_softmax_fwd", blk.E * (8 * H + 1) + blk.n_dst * 8):
+            L.call("regnn_edge_softmax_fwd", L.ptr(blk.csr_ptr), L.ptr(self.s), L.ptr(rel),
+                   L.ptr(t), L.ptr(gmax), float(eps), blk.n_dst, H, L.ptr(a), gp.ptr, L.stream())
+        y = head_spmm(blk, a, self.x).reshape(blk.n_dst, H * D)
+        if bias is not None:
+            y = y + bias
+        if residual is not None:
+            y = y + residual
+        if ln is not None:
+            y = torch.nn.functional.layer_norm(y, (H * D,), ln[0], ln[1], ln[2])
+        return torch.relu(y) if relu else y
+
+
+def _amax1(t):
+    if t.numel():
+        return t.amax().reshape(1)
+    return torch.full((1,), float("-inf"), dtype=torch.float32, device=t.device)
+
+
+def _head_dots(x, att):
+    """<x[n,h,:], att[h,:]> [n, H] fp32 in one read of x (regnn_attn_dots_fwd), no [n, H, D]
+    product tensor"""
+    return _AttnDots.apply(x.detach().float(), att.detach(), att.detach())[0]
+
+
+@torch.no_grad()
+def mag_attn_fwd(blk, x, kind, tab, slope, el=None, er=None, att=None, xd=None):
+    """regnn_mag_attn_fwd over a row block -> (acc [n_dst, H, D] NOT divided by rsum,
+    rmax [n_dst, H], rsum [n_dst, H]); a row without entries: 0, -inf, 0. x [n_src, H, D] fp32.
+    kind "gat": er [n_dst, H] and either el [n_src, H] or att = attn_l [1, H, D] (el re-formed
+    from the gathered rows); kind "gatv2": att [1, H, D] and xd [n_dst, H, D]."""
+    N, H, D = x.shape
+    if x.dtype != torch.float32:
+        raise TypeError(f"regnn_mag_attn_fwd reads fp32 rows, got {x.dtype}")
+    dev, n = x.device, blk.n_dst
+    if N < getattr(blk, "n_src", 0) or blk.csr_ptr.numel() != n + 1:
+        raise ValueError(f"x holds {N} rows, the block names {getattr(blk, 'n_src', 0)} sources "
+                         f"and {n} rows (ptr: {blk.csr_ptr.numel()})")
+    f = lambda v, *s: None if v is None else v.detach().float().reshape(*s).contiguous()  # noqa: E731
+    t = f(tab, -1, H)
+    rel = blk.pack.rel_csr if t is not None else None
+    x = x.contiguous()
+    acc = torch.empty(n, H, D, dtype=torch.float32, device=dev)
+    rmax = torch.empty(n, H, dtype=torch.float32, device=dev)
+    rsum = torch.empty(n, H, dtype=torch.float32, device=dev)
+    gp = _GatPlan(getattr(blk, "csr_plan", None), H * D + 2 * H, dev)
+    if kind == "gatv2":
+        args = (1, None, None, L.ptr(f(att, H, D)), L.ptr(x), L.ptr(f(xd, n, H * D)))
+    elif kind == "gat":
+        args = (0, L.ptr(f(el, N, H)), L.ptr(f(er, n, H)),
+                L.ptr(None if el is not None else f(att, H, D)), L.ptr(x), None)
+    else:
+        raise ValueError(kind)
+    with timed("mag_attn_fwd", blk.E * (H * D * 4 + 5) + n * (2 * H * D * 4 + 12 * H + 4)):
+        L.call("regnn_mag_attn_fwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx), L.ptr(rel), L.ptr(t),
+               *args, L.ptr(acc), L.ptr(rmax), L.ptr(rsum), n, H, D, float(slope), gp.ptr,
+               L.stream())
+    return acc, rmax, rsum
+
+
+@torch.no_grad()
+def mag_attn_scores(blk, x_all, x_own, kind, tab, slope, att_src=None, att_dst=None, att=None,
+                    form=None):
+    """First half of a mag attention layer at inference over a row block (csr_ptr / csr_idx /
+    csr_plan / pack.rel_csr / n_dst / E: inference.RowBlock, a RelGraph with a pack attribute).
+
+    x_all [n_src, H, D]: the projected rows of every source; x_own [n_dst, H, D]: those of the
+    block's rows (lin_dst is lin_src). kind "gat": scores LeakyReLU(<att_src, x[u]> +
+    <att_dst, x[v]> + tab[rel]) (mag/regnn_layers.py:289-301); "gatv2": <att, LeakyReLU(x[u] +
+    x[v])> + tab[rel] (:399-408). form "fused": regnn_mag_attn_fwd, one pass that stores no
+    [E, H] tensor; "chain": the per-edge scores of the existing operators. None: MAG_ATTN_FORM's
+    choice where the fused kernel takes the shape, the chain otherwise (never the host)."""
+    if kind not in ("gat", "gatv2"):
+        raise ValueError(kind)
+    N, H, D = x_all.shape
+    x_all, x_own = x_all.contiguous(), x_own.contiguous()
+    ok = mag_attn_fused_ok(kind, H, D, x_all)
+    if form is None:
+        form = MAG_ATTN_FORM[kind] if ok else "chain"
+    if form not in ("fused", "chain"):
+        raise ValueError(form)
+    if form == "fused" and not ok:
+        raise ValueError(f"regnn_mag_attn_fwd does not take kind {kind} with H = {H}, D = {D}, "
+                         f"{x_all.dtype}")
+    dev = x_all.device
+    t = None if tab is None else tab.detach().float().contiguous()
+    rel = blk.pack.rel_csr if t is not None else None
+    n = blk.n_dst
+    st = MagAttn(form, blk, H, D)
+    if kind == "gat":
+        er = _head_dots(x_own, att_dst)
+    if form == "fused":
+        if kind == "gatv2":
+            kw = dict(att=att, xd=x_own)
+        elif _vec_dots_ok(D):        # el re-formed from the gathered row: one access per entry
+            kw = dict(er=er, att=att_src)
+        else:
+            kw = dict(er=er, el=_head_dots(x_all, att_src))
+        st.acc, st.rmax, st.rsum = mag_attn_fwd(blk, x_all, kind, tab, slope, **kw)
+        st.gmax = _amax1(st.rmax)
+        return st
+    st.x = x_all
+    s = torch.empty(blk.E, H, dtype=torch.float32, device=dev)
+    if kind == "gat":
+        el = _head_dots(x_all, att_src)
+        L.call("regnn_gat_scores", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx), L.ptr(rel), L.ptr(t),
+               L.ptr(el), L.ptr(er), n, H, float(slope), L.ptr(s), L.stream())
+        st.s, st.rel_tab = s, (None, None)           # the table is inside the scores
+        st.gmax = _amax1(s)
+    else:
+        st.s = gatv2_scores(blk, x_all.float(), x_own.float(), att.detach(), slope)
+        st.rel_tab = (rel, t)
+        st.gmax = _amax1(st.s if t is None else st.s + t[rel.long()])
+    return st
+
+
+@torch.no_grad()
+def mag_attn_epilogue(acc, rmax, rsum, gmax, bias=None, residual=None, ln=None, relu=False,
+                      eps=1e-16):
+    """y [n, H * D] = acc / (rsum + eps exp(gmax - rmax)) + bias + residual, LayerNorm (ln =
+    (weight, bias, eps)), relu: regnn_mag_attn_epilogue, the second half of the fused form. gmax:
+    one float on the device (the global maximum, already reduced over ranks)."""
+    n, H, D = acc.shape
+    y = torch.empty(n, H * D, dtype=torch.float32, device=acc.device)
+    f = lambda v: None if v is None else v.detach().float().contiguous()   # noqa: E731
+    lw, lb, le = (None, None, 0.0) if ln is None else ln
+    for name, v, size in (("rmax", rmax, n * H), ("rsum", rsum, n * H), ("bias", bias, H * D),
+                          ("residual", residual, n * H * D), ("ln weight", lw, H * D),
+                          ("ln bias", lb, H * D)):
+        if v is not None and v.numel() != size:
+            raise ValueError(f"mag_attn_epilogue: {name} holds {v.numel()} elements, not {size}")
+    acc, rmax, rsum = f(acc), f(rmax), f(rsum)
+    flags = (1 if ln is not None else 0) | (2 if relu else 0)
+    with timed("mag_attn_epilogue", n * (H * D * 4 * (3 if residual is not None else 2) + 8 * H)):
+        L.call("regnn_mag_attn_epilogue", L.ptr(acc), L.ptr(rmax), L.ptr(rsum),
+               L.ptr(gmax.reshape(1).float().contiguous()), float(eps), L.ptr(f(bias)),
+               L.ptr(f(residual)), L.ptr(f(lw)), L.ptr(f(lb)), float(le), flags, n, H, D,
+               L.ptr(y), L.stream())
+    return y
+
+
+def mag_attn_infer(blk, x_all, x_own, kind, tab, slope, att_src=None, att_dst=None, att=None,
+                   bias=None, residual=None, ln=None, relu=False, gmax=None, form=None):
+    """One mag attention layer at inference over a row block: mag_attn_scores, then finish() with
+    gmax (None: the block's own maximum, i.e. one rank) -> y [n_dst, H * D]."""
+    st = mag_attn_scores(blk, x_all, x_own, kind, tab, slope, att_src, att_dst, att, form)
+    return st.finish(gmax, bias, residual, ln, relu)
+
+
+# ---------------------------------------------------------------------------------------------
 def col_sum(x):
     """x.sum(0) for a tall row-major fp32 matrix, deterministic (HIP col_sum + slab reduce)."""
     x = x.contiguous().float()
