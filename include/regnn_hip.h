@@ -315,6 +315,27 @@ int regnn_gat_fused_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* r
  * bitwise the el passed) instead of reading el: one random access per edge instead of two.
  * el must then be regnn_attn_dots_fwd(x, attn_l, ...)'s. */
 
+/* regnn_gat_fused_fwd with the attention dropout of layer/REGATConv.py:88 inside the pass (the
+ * training forward; the dropped attention is never written):
+ *   out[v,h,:] = sum_{e: u->v} w(e,h) * softmax_v(e)[h] * x[u,h,:],  w = keep(e,h) ? drop_scale : 0
+ * The softmax is the undropped one: the mask multiplies only the term an edge adds to the
+ * accumulator, so the running max / sum, the chunk partials [acc | max | sum] and lse are
+ * regnn_gat_fused_fwd's (a destination whose entries are all dropped has an exact zero row and a
+ * finite lse). Mask: the regnn_spmm_fwd_dropout spec over the [E, Hq] fp32 matrix of (CSR edge
+ * position e, head h), Hq = max(4, H rounded up to a multiple of 4), EV = 4: c = e * (Hq / 4) +
+ * h / 4, draw h % 4 of that vector (columns H..Hq-1 are not read). It depends on (*drop_seed, e,
+ * h) alone: not on the plan, the lane tier or the grid. *drop_seed is read on the device at
+ * execution. 8-bit draws when drop_keep16 % 256 == 0, else 16-bit.
+ * drop_seed NULL or drop_keep16 > 65536: REGNN_EINVAL; H no power of two <= 32 (the shapes
+ * regnn_gat_attn_lse, the backward's first step, takes): REGNN_EUNSUPPORTED. */
+int regnn_gat_fused_fwd_drop(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                             const float* ee_table, const float* el, const float* er,
+                             const void* x, void* out, float* lse, int64_t n_seg, int32_t H,
+                             int32_t D, float slope, int32_t dtype, const float* attn_l,
+                             const regnn_seg_plan* plan, const uint64_t* drop_seed,
+                             uint32_t drop_keep16, float drop_scale,
+                             hipStream_t stream);  /* partial width H*D + 2H */
+
 /* The attention a[e,h] = exp(e[h] - lse[v,h]) (CSR edge order) of regnn_gat_fused_fwd, re-formed
  * for the backward. H a power of two <= 32. */
 int regnn_gat_attn_lse(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
@@ -337,6 +358,20 @@ int regnn_spmm_heads_bwd(const int32_t* ptr, const int32_t* idx, const int32_t* 
                          const float* a, const void* g, const void* x, void* gx, float* ga,
                          int64_t n_seg, int32_t H, int32_t D, int32_t dtype,
                          const regnn_seg_plan* plan, hipStream_t stream);  /* partial width H*D */
+
+/* The backward of regnn_gat_fused_fwd_drop's aggregation: regnn_spmm_heads_bwd with a the
+ * UNDROPPED attention (regnn_gat_attn_lse's) and the same mask factor w, taken at the edge's CSR
+ * position perm[e] (the [E, Hq] indexing above; same seed, threshold and scale as the forward):
+ *   gx[u,h,:] = sum_{e: u->v} w(perm[e],h) * a[perm[e],h] * g[v,h,:]
+ *   ga[perm[e],h] = w(perm[e],h) * <g[v,h,:], x[u,h,:]>
+ * ga is d loss / d a, so regnn_gat_softmax_bwd and regnn_segment_sum follow unchanged on the
+ * undropped a: the exact VJP. Fixed summation order, no atomics. Refusals as the forward's. */
+int regnn_spmm_heads_bwd_drop(const int32_t* ptr, const int32_t* idx, const int32_t* perm,
+                              const float* a, const void* g, const void* x, void* gx, float* ga,
+                              int64_t n_seg, int32_t H, int32_t D, int32_t dtype,
+                              const regnn_seg_plan* plan, const uint64_t* drop_seed,
+                              uint32_t drop_keep16, float drop_scale,
+                              hipStream_t stream);  /* partial width H*D */
 
 /* out[s,h] = sum_{e in seg s} vals[(perm ? perm[e] : e)*H + h]  (segment sum of edge values,
  * e.g. d loss / d el over the CSC). */

@@ -113,11 +113,31 @@ struct HeadArgs {
     int H, D;
 };
 
+// regnn_spmm_heads_bwd_drop: the attention dropout of the fused forward (a struct of its own: the
+// kernel arguments of the undropped instantiations stay as they are)
+struct HeadDropArgs : HeadArgs {
+    const uint64_t* dseed;
+    uint32_t dthresh;
+    float dscale;
+};
+
 // CH: the units are the chunks of long segments (fp32 partial rows of the sums); otherwise the
 // segments, long ones skipped. The per-edge ga of the backward is written either way.
-template <typename T, int LPR, int NV, bool BWD, bool CH>
-__global__ void __launch_bounds__(kBlock) spmm_heads_kernel(HeadArgs p, LongPlan P) {
+// DR (backward only): a is the undropped attention and the mask factor w_e = m_e / keep of
+// attn_drop_w (DR-bit draws) at the edge's CSR position perm[e] multiplies both results:
+// gx += w_e a_e g[v], ga[e] = w_e <g[v], x[u]> (the VJP of out = sum_e w_e a_e x_u).
+template <typename T, int LPR, int NV, bool BWD, bool CH, int DR = 0>
+__global__ void __launch_bounds__(kBlock)
+spmm_heads_kernel(std::conditional_t<DR != 0, HeadDropArgs, HeadArgs> p, LongPlan P) {
     constexpr int EV = Vec<T>::N;
+    static_assert(DR == 0 || DR == 8 || DR == 16, "draw width");
+    static_assert(DR == 0 || BWD, "dropout: the backward (the forward is gat_fused_fwd_kernel)");
+    uint32_t dkey = 0;
+    int dnvec = 1;
+    if constexpr (DR != 0) {
+        dkey = drop_key(p.dseed);
+        dnvec = attn_drop_nvec(p.H);
+    }
 #ifdef REGNN_HEADS_UN
     constexpr int UN = NV <= 2 ? REGNN_HEADS_UN : (NV <= 4 ? 4 : 2);
 #else
@@ -185,6 +205,11 @@ __global__ void __launch_bounds__(kBlock) spmm_heads_kernel(HeadArgs p, LongPlan
                 for (int u = 0; u < UN; ++u) {
 #pragma unroll
                     for (int q = 0; q < NV; ++q) {
+                        float mw = 1.f;
+                        if constexpr (DR != 0) {
+                            mw = attn_drop_w<DR>(dkey, p.dthresh, p.dscale, ekk[u], dnvec, head[q]);
+                            w[u][q] *= mw;
+                        }
 #pragma unroll
                         for (int t = 0; t < EV; ++t) acc[q][t] = fmaf(w[u][q], v[u][q][t], acc[q][t]);
                         if constexpr (BWD) {
@@ -193,6 +218,7 @@ __global__ void __launch_bounds__(kBlock) spmm_heads_kernel(HeadArgs p, LongPlan
 #pragma unroll
                             for (int t = 0; t < EV; ++t) d = fmaf(v[u][q][t], sx[q][t], d);
                             for (int m = vph >> 1; m > 0; m >>= 1) d += __shfl_xor(d, m, 64);
+                            if constexpr (DR != 0) d *= mw;
                             if (k0 + u < cnt && o < F && (lane & (vph - 1)) == 0)
                                 p.ga[(int64_t)ekk[u] * p.H + head[q]] = d;
                         }
@@ -220,8 +246,9 @@ __global__ void __launch_bounds__(kBlock) spmm_heads_kernel(HeadArgs p, LongPlan
     }
 }
 
-template <typename T, bool BWD>
-int dispatch_heads(HeadArgs p, const regnn_seg_plan* pl, hipStream_t stream) {
+template <typename T, bool BWD, int DR = 0>
+int dispatch_heads(std::conditional_t<DR != 0, HeadDropArgs, HeadArgs> p, const regnn_seg_plan* pl,
+                   hipStream_t stream) {
     constexpr int EV = Vec<T>::N;
     const int F = p.H * p.D;
     if (p.D <= 0 || p.D % EV || p.H <= 0) return REGNN_EUNSUPPORTED;
@@ -231,11 +258,11 @@ int dispatch_heads(HeadArgs p, const regnn_seg_plan* pl, hipStream_t stream) {
     const LongPlan P = long_plan(pl);
 #define REGNN_HEADS(LPR, NV)                                                                    \
     if (nvec <= (LPR) * (NV) && vph <= (LPR)) {                                                 \
-        hipLaunchKernelGGL((spmm_heads_kernel<T, LPR, NV, BWD, false>),                         \
+        hipLaunchKernelGGL((spmm_heads_kernel<T, LPR, NV, BWD, false, DR>),                     \
                            dim3(grid_for(p.n_seg, kBlock / (LPR))), dim3(kBlock), 0, stream, p, P); \
         REGNN_LAUNCH_CHECK();                                                                   \
         if (P.n_chunk > 0) {                                                                    \
-            hipLaunchKernelGGL((spmm_heads_kernel<T, LPR, NV, BWD, true>),                      \
+            hipLaunchKernelGGL((spmm_heads_kernel<T, LPR, NV, BWD, true, DR>),                  \
                                dim3(grid_for(P.n_chunk, kBlock / (LPR))), dim3(kBlock), 0, stream, \
                                p, P);                                                           \
             const int64_t base = run_tree(pl, 0, F, F, p.H, p.D, stream);                       \
@@ -534,8 +561,9 @@ gat_attn_lse_group(const int32_t* __restrict__ ptr, const int32_t* __restrict__ 
     }
 }
 
-template <typename T>
-int dispatch_gat_fused(GatFusedArgs p, const regnn_seg_plan* pl, hipStream_t stream) {
+template <typename T, int DR = 0>
+int dispatch_gat_fused(std::conditional_t<DR != 0, GatFusedDropArgs, GatFusedArgs> p,
+                       const regnn_seg_plan* pl, hipStream_t stream) {
     constexpr int EV = Vec<T>::N;
     constexpr int SCX = EV == 4 ? kScoreElx : kScoreEl;    // (the ELX form: fp32 rows only)
     const int F = p.H * p.D;
@@ -550,21 +578,23 @@ int dispatch_gat_fused(GatFusedArgs p, const regnn_seg_plan* pl, hipStream_t str
         const bool elx = std::is_same<T, float>::value && p.al && attn_dots_vec_ok(p.D) &&    \
                          p.D / 4 <= (LPR);                                                    \
         if (elx)                                                                              \
-            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, SCX, false>),         \
+            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, SCX, false, DR>),     \
                                dim3(grid_for(p.n_seg, kBlock / (LPR))), dim3(kBlock), 0, stream, \
                                p, P);                                                         \
         else                                                                                  \
-            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, kScoreEl, false>),    \
+            hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, false, kScoreEl, false,      \
+                                                     DR>),                                    \
                                dim3(grid_for(p.n_seg, kBlock / (LPR))), dim3(kBlock), 0, stream, \
                                p, P);                                                         \
         REGNN_LAUNCH_CHECK();                                                                 \
         if (P.n_chunk > 0) {                                                                  \
             if (elx)                                                                          \
-                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, SCX, false>),      \
+                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, SCX, false, DR>),  \
                                    dim3(grid_for(P.n_chunk, kBlock / (LPR))), dim3(kBlock), 0, \
                                    stream, p, P);                                             \
             else                                                                              \
-                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, kScoreEl, false>), \
+                hipLaunchKernelGGL((gat_fused_fwd_kernel<T, LPR, NV, true, kScoreEl, false,   \
+                                                         DR>),                                \
                                    dim3(grid_for(P.n_chunk, kBlock / (LPR))), dim3(kBlock), 0, \
                                    stream, p, P);                                             \
             const int64_t base = run_tree(pl, 1, F + 2 * p.H, F, p.H, p.D, stream);           \
@@ -851,6 +881,30 @@ int regnn_gat_fused_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* r
     return REGNN_EUNSUPPORTED;
 }
 
+int regnn_gat_fused_fwd_drop(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                             const float* ee_table, const float* el, const float* er,
+                             const void* x, void* out, float* lse, int64_t n_seg, int32_t H,
+                             int32_t D, float slope, int32_t dtype, const float* attn_l,
+                             const regnn_seg_plan* plan, const uint64_t* drop_seed,
+                             uint32_t drop_keep16, float drop_scale, hipStream_t stream) {
+    if (!drop_seed || drop_keep16 > 65536u) return REGNN_EINVAL;
+    if (!ptr || !idx || !el || !er || !x || !out || !lse || n_seg < 0 || (ee_table && !rel))
+        return REGNN_EINVAL;
+    if (gat_log2(H) < 0) return REGNN_EUNSUPPORTED;    // as regnn_gat_attn_lse, the backward's
+    if (n_seg == 0) return REGNN_OK;
+    if (const int rc = check_plan(plan, int64_t(H) * D + 2 * H)) return rc;
+    GatFusedDropArgs p{{ptr, idx, rel, ee_table, el, er, x, out, lse, attn_l, n_seg, H, D, slope},
+                       drop_seed, drop_keep16, drop_scale};
+    const bool b8 = (drop_keep16 & 0xFFu) == 0;
+    if (dtype == REGNN_F32)
+        return b8 ? dispatch_gat_fused<float, 8>(p, plan, stream)
+                  : dispatch_gat_fused<float, 16>(p, plan, stream);
+    if (dtype == REGNN_BF16)
+        return b8 ? dispatch_gat_fused<bf16_t, 8>(p, plan, stream)
+                  : dispatch_gat_fused<bf16_t, 16>(p, plan, stream);
+    return REGNN_EUNSUPPORTED;
+}
+
 int regnn_gat_attn_lse(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
                        const float* ee_table, const float* el, const float* er, const float* lse,
                        int64_t n_seg, int32_t H, float slope, float* a, const regnn_seg_plan* plan,
@@ -897,6 +951,28 @@ int regnn_spmm_heads_bwd(const int32_t* ptr, const int32_t* idx, const int32_t* 
     HeadArgs p{ptr, idx, perm, a, g, x, gx, ga, n_seg, H, D};
     if (dtype == REGNN_F32) return dispatch_heads<float, true>(p, plan, stream);
     if (dtype == REGNN_BF16) return dispatch_heads<bf16_t, true>(p, plan, stream);
+    return REGNN_EUNSUPPORTED;
+}
+
+int regnn_spmm_heads_bwd_drop(const int32_t* ptr, const int32_t* idx, const int32_t* perm,
+                              const float* a, const void* g, const void* x, void* gx, float* ga,
+                              int64_t n_seg, int32_t H, int32_t D, int32_t dtype,
+                              const regnn_seg_plan* plan, const uint64_t* drop_seed,
+                              uint32_t drop_keep16, float drop_scale, hipStream_t stream) {
+    if (!drop_seed || drop_keep16 > 65536u) return REGNN_EINVAL;
+    if (!ptr || !idx || !a || !g || !x || !gx || !ga || n_seg < 0) return REGNN_EINVAL;
+    if (gat_log2(H) < 0) return REGNN_EUNSUPPORTED;
+    if (n_seg == 0) return REGNN_OK;
+    if (const int rc = check_plan(plan, int64_t(H) * D)) return rc;
+    HeadDropArgs p{{ptr, idx, perm, a, g, x, gx, ga, n_seg, H, D}, drop_seed, drop_keep16,
+                   drop_scale};
+    const bool b8 = (drop_keep16 & 0xFFu) == 0;
+    if (dtype == REGNN_F32)
+        return b8 ? dispatch_heads<float, true, 8>(p, plan, stream)
+                  : dispatch_heads<float, true, 16>(p, plan, stream);
+    if (dtype == REGNN_BF16)
+        return b8 ? dispatch_heads<bf16_t, true, 8>(p, plan, stream)
+                  : dispatch_heads<bf16_t, true, 16>(p, plan, stream);
     return REGNN_EUNSUPPORTED;
 }
 

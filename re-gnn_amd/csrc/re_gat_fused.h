@@ -4,6 +4,7 @@
 #pragma once
 #include "regnn_common.h"
 #include "re_segplan.h"
+#include <type_traits>
 
 namespace regnn {
 
@@ -36,6 +37,37 @@ struct GatFusedArgs {
     float* rmax;        // [n_seg, H] running max of the row's scores (-inf: no entries)
     float* rsum;        // [n_seg, H] sum_e exp(s_e - rmax)
 };
+
+// regnn_gat_fused_fwd_drop: the attention dropout's seed (device memory), threshold and scale.
+// A struct of its own, so the kernel arguments of the undropped instantiations stay as they are.
+struct GatFusedDropArgs : GatFusedArgs {
+    const uint64_t* dseed;
+    uint32_t dthresh;
+    float dscale;
+};
+
+// Attention dropout (regnn_hip.h, regnn_gat_fused_fwd_drop): the fused-dropout mask of
+// regnn_common.h (drop_key / drop_apply, EV = 4) over the [E, Hq] matrix of (CSR edge position,
+// head), Hq = max(4, H rounded up to a multiple of 4). Returns the factor of element (e, h):
+// scale when kept, 0 when dropped. One hash per (edge, 4-head group), a second for heads 2, 3 of
+// the group with 16-bit draws.
+__device__ __forceinline__ int attn_drop_nvec(int H) { return H <= 4 ? 1 : (H + 3) >> 2; }
+
+template <int BITS>
+__device__ __forceinline__ float attn_drop_w(uint32_t key, uint32_t thresh, float scale, int e,
+                                             int nvec, int h) {
+    const uint64_t c = uint64_t(e) * uint64_t(nvec) + uint64_t(h >> 2);
+    const uint32_t hi = uint32_t(c >> 32);
+    uint32_t x = fmix32(uint32_t(c) ^ key ^ ((hi << 16) | (hi >> 16)));
+    const int b = h & 3;
+    if constexpr (BITS == 16) {
+        const uint32_t x1 = fmix32(x + 0x9E3779B9u);
+        x = (b & 2) ? x1 : x;
+        return ((b & 1) ? x >> 16 : x & 0xFFFFu) < thresh ? scale : 0.f;
+    } else {
+        return ((x >> (8 * b)) & 0xFFu) < (thresh >> 8) ? scale : 0.f;
+    }
+}
 
 // how a lane forms the score of an edge
 constexpr int kScoreEl = 0;      // el[u,h] read per edge
@@ -74,9 +106,21 @@ inline bool attn_dots_vec_ok(int D) {
 // CH: the units are the chunks of long segments (partial rows [acc | max | sum], unnormalised);
 // otherwise the segments, long ones skipped. SC: the score form (kScore*). INF: the per-segment
 // pass writes the unnormalised accumulator with rmax / rsum instead of out / lse.
-template <typename T, int LPR, int NV, bool CH, int SC, bool INF>
-__global__ void __launch_bounds__(kBlock) gat_fused_fwd_kernel(GatFusedArgs p, LongPlan P) {
+// DR: attention dropout with DR-bit draws (0: none). The mask factor multiplies only the term an
+// edge adds to the accumulator: running max, running sum, lse and the chunk partials' max / sum
+// are those of the undropped softmax, so out = sum_e (m_e / keep) a_e x_u with a undropped.
+template <typename T, int LPR, int NV, bool CH, int SC, bool INF, int DR = 0>
+__global__ void __launch_bounds__(kBlock)
+gat_fused_fwd_kernel(std::conditional_t<DR != 0, GatFusedDropArgs, GatFusedArgs> p, LongPlan P) {
     constexpr int EV = Vec<T>::N;
+    static_assert(DR == 0 || DR == 8 || DR == 16, "draw width");
+    static_assert(DR == 0 || !INF, "dropout: the training forward");
+    uint32_t dkey = 0;
+    int dnvec = 1;
+    if constexpr (DR != 0) {
+        dkey = drop_key(p.dseed);
+        dnvec = attn_drop_nvec(p.H);
+    }
     constexpr bool ELX = SC == kScoreElx, V2 = SC == kScoreV2;
     static_assert(SC == kScoreEl || EV == 4, "ELX / GATv2: fp32 rows");
 #ifdef REGNN_GATF_UN
@@ -182,8 +226,12 @@ __global__ void __launch_bounds__(kBlock) gat_fused_fwd_kernel(GatFusedArgs p, L
                         const bool grow = d > 0.f;                   // new running max
                         const float ex = __expf(grow ? -d : d);
                         const float sa = grow ? ex : 1.f, sv = grow ? 1.f : ex;
+                        float sw = sv;
+                        if constexpr (DR != 0)
+                            sw *= attn_drop_w<DR>(dkey, p.dthresh, p.dscale, e0 + k0 + u, dnvec,
+                                                  head[q]);
 #pragma unroll
-                        for (int t = 0; t < EV; ++t) acc[q][t] = fmaf(acc[q][t], sa, sv * v[u][q][t]);
+                        for (int t = 0; t < EV; ++t) acc[q][t] = fmaf(acc[q][t], sa, sw * v[u][q][t]);
                         s[q] = fmaf(s[q], sa, sv);
                         m[q] = grow ? sc[u][q] : m[q];
                     }

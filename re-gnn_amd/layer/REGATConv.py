@@ -1,6 +1,9 @@
 """REGATConv on MI355X — drop-in for layer/REGATConv.py:10-100. The u_add_v SDDMM + relation bias +
 LeakyReLU + per-destination edge softmax is one HIP kernel (forward and backward), the per-head
-aggregation another, the per-head el/er dots a third; torch does the fc projection (hipBLASLt)."""
+aggregation another, the per-head el/er dots a third; torch does the fc projection (hipBLASLt).
+Training with attn_drop > 0 runs attention -> nn.Dropout -> aggregation as three operators, or,
+with ops.ATTN_DROP["mode"] = "fused" (REGNN_GAT_ATTN_DROP=fused), the dropout inside the fused
+forward and its backward (ops.gat_fused(attn_drop=p))."""
 import torch as th
 from torch import nn
 from torch.nn import init
@@ -64,9 +67,14 @@ class REGATConv(nn.Module):
             pack = rg.rel_pack(edge_feats, num_rel=self.num_etypes)
         slope = self.leaky_relu.negative_slope
         if self.training and self.attn_drop.p > 0:
-            a = ops.gat_attention(rg, el, er, tab, pack, slope)                    # :80-88
-            a = self.attn_drop(a)                                                  # :88
-            rst = ops.head_spmm(rg, a, ft)                                         # :90-92
+            if ops.ATTN_DROP["mode"] == "fused" and ops.gat_fused_ok(self.num_heads):
+                # the dropout inside the fused pass (this build's hash mask, not torch's stream)
+                rst = ops.gat_fused(rg, el, er, ft, tab, pack, slope, attn_l=self.attn_l,
+                                    attn_drop=self.attn_drop.p)                    # :80-92
+            else:
+                a = ops.gat_attention(rg, el, er, tab, pack, slope)                # :80-88
+                a = self.attn_drop(a)                                              # :88
+                rst = ops.head_spmm(rg, a, ft)                                     # :90-92
         else:
             # no attention dropout: scores, softmax and aggregation in one pass (:80-92)
             rst = ops.gat_fused(rg, el, er, ft, tab, pack, slope, attn_l=self.attn_l)

@@ -1380,10 +1380,16 @@ class _GatFused(torch.autograd.Function):
     """out[v,h,:] = sum_{e: u->v} edge_softmax(LeakyReLU(el[u]+er[v]+ee[rel]))[e,h] * ft[u,h,:]
     in one pass (regnn_gat_fused_fwd, online softmax; the [E, H] attention is not stored). The
     backward re-forms the attention from the per-(destination, head) log-sum-exp
-    (regnn_gat_attn_lse) and runs the unfused backward kernels."""
+    (regnn_gat_attn_lse) and runs the unfused backward kernels.
+
+    drop = drop_request(...)'s (seed tensor, keep16, scale), or None: the attention dropout of
+    layer/REGATConv.py:88 as a hash mask over (CSR edge position, head) inside the same pass
+    (regnn_gat_fused_fwd_drop). The softmax stays the undropped one; the backward masks the
+    aggregation's two gradients (regnn_spmm_heads_bwd_drop, the seed tensor saved) and runs the
+    rest unchanged on the undropped attention."""
 
     @staticmethod
-    def forward(ctx, el, er, ee_tab, ft, rg, pack, slope, attn_l):
+    def forward(ctx, el, er, ee_tab, ft, rg, pack, slope, attn_l, drop=None):
         N, H, D = ft.shape
         el, er, ft = el.contiguous().float(), er.contiguous().float(), ft.contiguous()
         al = None if attn_l is None else attn_l.detach().reshape(H, D).float().contiguous()
@@ -1392,20 +1398,30 @@ class _GatFused(torch.autograd.Function):
         out = torch.empty(rg.n_dst, H, D, dtype=ft.dtype, device=ft.device)
         lse = torch.empty(rg.n_dst, H, dtype=torch.float32, device=ft.device)
         s_ = ft.element_size()
-        with timed("gat_fused_fwd", rg.E * (H * D * s_ + 4 * H + 5) +
-                   rg.n_dst * (H * D * s_ + 8 * H + 4)):
-            gp = _GatPlan(getattr(rg, "csr_plan", None), H * D + 2 * H, ft.device)
-            L.call("regnn_gat_fused_fwd", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(rel),
-                   L.ptr(t), L.ptr(el), L.ptr(er), L.ptr(ft), L.ptr(out), L.ptr(lse), rg.n_dst, H,
-                   D, float(slope), L.dtype_code(ft), L.ptr(al), gp.ptr, L.stream())
+        nbytes = rg.E * (H * D * s_ + 4 * H + 5) + rg.n_dst * (H * D * s_ + 8 * H + 4)
+        if drop is None:
+            with timed("gat_fused_fwd", nbytes):
+                gp = _GatPlan(getattr(rg, "csr_plan", None), H * D + 2 * H, ft.device)
+                L.call("regnn_gat_fused_fwd", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(rel),
+                       L.ptr(t), L.ptr(el), L.ptr(er), L.ptr(ft), L.ptr(out), L.ptr(lse),
+                       rg.n_dst, H, D, float(slope), L.dtype_code(ft), L.ptr(al), gp.ptr,
+                       L.stream())
+        else:
+            with timed("gat_fused_fwd_drop", nbytes + 8):
+                gp = _GatPlan(getattr(rg, "csr_plan", None), H * D + 2 * H, ft.device)
+                L.call("regnn_gat_fused_fwd_drop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
+                       L.ptr(rel), L.ptr(t), L.ptr(el), L.ptr(er), L.ptr(ft), L.ptr(out),
+                       L.ptr(lse), rg.n_dst, H, D, float(slope), L.dtype_code(ft), L.ptr(al),
+                       gp.ptr, *_drop_args(drop), L.stream())
         ctx.rg, ctx.pack, ctx.slope = rg, pack, slope
         ctx.tab_shape = None if ee_tab is None else ee_tab.shape
-        ctx.save_for_backward(el, er, t, ft, lse)
+        ctx.drop = None if drop is None else drop[1:]
+        ctx.save_for_backward(el, er, t, ft, lse, None if drop is None else drop[0])
         return out
 
     @staticmethod
     def backward(ctx, gy):
-        el, er, t, ft, lse = ctx.saved_tensors
+        el, er, t, ft, lse, seed = ctx.saved_tensors
         rg, pack, slope = ctx.rg, ctx.pack, ctx.slope
         N, H, D = ft.shape
         rel = pack.rel_csr if t is not None else None
@@ -1419,12 +1435,20 @@ class _GatFused(torch.autograd.Function):
         gft = torch.empty_like(ft)
         ga = torch.empty_like(a)
         s_ = ft.element_size()
-        with timed("spmm_heads_bwd",
-                   rg.E * (H * D * s_ + 8 * H + 8) + rg.n_src * (2 * H * D * s_ + 4)):
-            gq = _GatPlan(getattr(rg, "csc_plan", None), H * D, ft.device)
-            L.call("regnn_spmm_heads_bwd", L.ptr(rg.csc_ptr), L.ptr(rg.csc_idx),
-                   L.ptr(rg.csc2csr), L.ptr(a), L.ptr(gy), L.ptr(ft), L.ptr(gft), L.ptr(ga),
-                   rg.n_src, H, D, L.dtype_code(ft), gq.ptr, L.stream())
+        nbytes = rg.E * (H * D * s_ + 8 * H + 8) + rg.n_src * (2 * H * D * s_ + 4)
+        if seed is None:
+            with timed("spmm_heads_bwd", nbytes):
+                gq = _GatPlan(getattr(rg, "csc_plan", None), H * D, ft.device)
+                L.call("regnn_spmm_heads_bwd", L.ptr(rg.csc_ptr), L.ptr(rg.csc_idx),
+                       L.ptr(rg.csc2csr), L.ptr(a), L.ptr(gy), L.ptr(ft), L.ptr(gft), L.ptr(ga),
+                       rg.n_src, H, D, L.dtype_code(ft), gq.ptr, L.stream())
+        else:
+            with timed("spmm_heads_bwd_drop", nbytes + 8):
+                gq = _GatPlan(getattr(rg, "csc_plan", None), H * D, ft.device)
+                L.call("regnn_spmm_heads_bwd_drop", L.ptr(rg.csc_ptr), L.ptr(rg.csc_idx),
+                       L.ptr(rg.csc2csr), L.ptr(a), L.ptr(gy), L.ptr(ft), L.ptr(gft), L.ptr(ga),
+                       rg.n_src, H, D, L.dtype_code(ft), gq.ptr, L.ptr(seed), *ctx.drop,
+                       L.stream())
         gs = torch.empty_like(a)
         ger = torch.empty_like(er)
         n_rel = t.shape[0] if t is not None else 0
@@ -1439,17 +1463,44 @@ class _GatFused(torch.autograd.Function):
         L.call("regnn_segment_sum", L.ptr(rg.csc_ptr), L.ptr(rg.csc2csr), L.ptr(gs), rg.n_src, H,
                L.ptr(gel), gq.ptr, L.stream())
         g_tab = _reduce(slab, n_rel * H).view(ctx.tab_shape) if slab is not None else None
-        return gel, ger, g_tab, gft, None, None, None, None
+        return gel, ger, g_tab, gft, None, None, None, None, None
 
 
-def gat_fused(rg, el, er, ft, ee_tab=None, pack=None, slope=0.2, attn_l=None):
-    """layer/REGATConv.py:80-92 without attention dropout, as one fused forward pass (H a power of
-    two <= 32; otherwise the unfused gat_attention + head_spmm). With attn_l (el then being
-    attn_dots(ft, attn_l, ...)'s) the kernel re-forms el from the rows it gathers, bitwise the
-    same, instead of reading it per edge (fp32 rows, D / 4 a power of two)."""
+# REGATConv's attention dropout in training: "fused" (inside ops.gat_fused, the hash mask of
+# regnn_gat_fused_fwd_drop) or "torch" (gat_attention -> nn.Dropout -> head_spmm: torch's stream).
+# Default by measurement (tools/gat_drop_time.py): on mag_like(1), 8 x 64, a
+# layer step takes 52.8 ms fused against 50.9 ms at p = 0.6 (51.0 against 50.8 at p = 0.5); the
+# fused form's gain is memory (1 % less at the peak) and a step that repeats from its seed.
+ATTN_DROP = {"mode": os.environ.get("REGNN_GAT_ATTN_DROP", "torch")}
+
+
+def gat_fused_ok(H):
+    """head counts the fused GAT forward takes (others run gat_attention + head_spmm)"""
+    return H >= 1 and H & (H - 1) == 0 and H <= 32
+
+
+def gat_fused(rg, el, er, ft, ee_tab=None, pack=None, slope=0.2, attn_l=None, attn_drop=0.0,
+              drop_seed=None):
+    """layer/REGATConv.py:80-92 as one fused forward pass (H a power of two <= 32; otherwise the
+    unfused gat_attention + head_spmm). With attn_l (el then being attn_dots(ft, attn_l, ...)'s)
+    the kernel re-forms el from the rows it gathers, bitwise the same, instead of reading it per
+    edge (fp32 rows, D / 4 a power of two).
+
+    attn_drop > 0: the attention dropout of :88 inside the same pass, out = sum_e (m_e / keep) a_e
+    ft_u with a the undropped edge softmax and m this build's hash mask over (CSR edge position,
+    head) (regnn_gat_fused_fwd_drop; torch's stream is not reproduced). drop_seed: a 1-element
+    int64 device tensor read at execution; None draws one from the per-device counter of
+    drop_request, as the SpMM dropout does. Generic head counts run torch's dropout between the
+    two unfused operators."""
     H = ft.shape[1]
-    if H & (H - 1) or H > 32:
-        return head_spmm(rg, gat_attention(rg, el, er, ee_tab, pack, slope), ft)
+    if not gat_fused_ok(H):
+        a = gat_attention(rg, el, er, ee_tab, pack, slope)
+        if attn_drop > 0:
+            a = torch.nn.functional.dropout(a, attn_drop, True)
+        return head_spmm(rg, a, ft)
+    if attn_drop > 0:
+        drop = drop_request(attn_drop, ft.device, drop_seed)
+        return _GatFused.apply(el, er, ee_tab, ft, rg, pack, slope, attn_l, drop)
     return _GatFused.apply(el, er, ee_tab, ft, rg, pack, slope, attn_l)
 
 
