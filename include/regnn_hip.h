@@ -20,7 +20,8 @@
  *  - Segments with more than `split` edges are processed by the long-segment plan
  *    (long_ids/chunk_long/chunk_off, see regnn_spmm_fwd) so hubs do not serialise one wave;
  *    split == 0 disables splitting. Results are bitwise reproducible run to run: no float
- *    atomics (except regnn_ns_spmm_bwd and regnn_ns_gat_bwd, the sampled-block backwards);
+ *    atomics (except regnn_ns_spmm_bwd, regnn_ns_gat_bwd and regnn_ns_gatv2_bwd, the
+ *    sampled-block backwards);
  *    cross-block reductions go through fixed-order slabs.
  */
 #ifndef REGNN_HIP_H
@@ -867,6 +868,64 @@ int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
                      const float* gy, float slope, int64_t cap_dst, int64_t n_src, int32_t H,
                      int32_t C, int32_t n_rel, float* g_ft, float* g_el, float* g_er, float* slab,
                      int32_t slab_rows, hipStream_t stream);
+
+/* mag REGATv2Conv attention over one device-sampled block, read as regnn_ns_hop leaves it (the
+ * same block contract as regnn_ns_gat_*: CSR ptr [cap_dst + 1], idx / rel [cap_e], rows past the
+ * live ones empty, the self loop last in its row, no host size anywhere). Replaces, for such a
+ * block, the reference's mag/regnn_layers.py:399-413 with the softmax of mag/utils.py:45-57 (the
+ * exact-size path's regnn_gatv2_score_fwd -> amax -> regnn_edge_softmax_fwd ->
+ * regnn_spmm_heads_fwd chain). For row v, entry e, u = idx_e:
+ *   pre[e,h,d] = xs[u,h,d] + xd[v,h,d]
+ *   s[e,h]     = sum_d att[h,d] LeakyReLU_slope(pre[e,h,d]) + tab[rel_e,h]   (no outer activation)
+ *   gmax       = max of s over every entry and head (ONE scalar, formed on the device)
+ *   a[e,h]     = exp(s[e,h] - gmax) / (sum_{e' in row v} exp(s[e',h] - gmax) + 1e-16)
+ *   out[v,h,:] = sum_{e in row v} a[e,h] xs[u,h,:]
+ * xs [>= n_src, H, C] is both the score operand and the message (in the mag layers lin_dst is
+ * lin_src and propagate sends x_src), xd [cap_dst, H, C], att [H, C], tab [n_rel, H] (NULL: no
+ * relation term; rel then unread), a [cap_e, H] (saved for the backward), out [cap_dst, H, C],
+ * work [REGNN_NS_GAT_WORK_FLOATS]; all fp32, rows 16-byte aligned. Two launches, as
+ * regnn_ns_gat_fwd: the scores (into a; a lane per (entry, head) reads the row's head slice by
+ * 16-byte loads and sums d = 0 .. C-1 in ONE fmaf chain from 0, the relation term added last)
+ * with one maximum per workgroup into work (every used slot rewritten by every call: nothing to
+ * reset between replays of a captured graph), then the softmax and aggregation launch that
+ * regnn_ns_gat_fwd runs: denominators and out summed in entry order, bitwise reproducible, exact
+ * zeros for rows without entries, an entry whose idx lies outside [0, n_src) takes no part.
+ *
+ * Backward (one launch), the maximum a constant and the 1e-16 kept, as regnn_ns_gat_bwd. With
+ * ga[e,h] = <gy[v,h,:], xs[u,h,:]> and D[v,h] = sum_row a ga:
+ *   gs[e,h]     = a (ga - D)
+ *   q[e,h,d]    = gs[e,h] att[h,d] (pre[e,h,d] > 0 ? 1 : slope)    (pre recomputed; at pre == 0
+ *                                                                   the slope, as torch)
+ *   g_xd[v,h,d] = sum_row q                     (every row written; empty rows 0)
+ *   att_slab[b][h,d] (optional) = workgroup b's partial of sum_e gs[e,h] LeakyReLU(pre[e,h,d])
+ *   tab_slab[b][r,h] (optional, with tab) = workgroup b's partial of sum_{rel_e = r} gs[e,h]
+ *   g_xs[u,h,d] += a[e,h] gy[v,h,d] + q[e,h,d]  over the entries with idx_e = u
+ * With a slab exactly slab_rows workgroups are launched and each writes its row of both (no zero
+ * fill needed); reduce with regnn_rel_reduce(att_slab, slab_rows, H * C) and (tab_slab, slab_rows,
+ * n_rel * H). g_xd, the slabs and so g_att / g_tab are bitwise reproducible for a fixed slab_rows:
+ * a wave takes its rows in a fixed order and their entries in entry order (g_xd and the g_att
+ * partial in the lane's registers, the relation bins in LDS), the waves' partials are added in
+ * wave order. Only g_xs takes form (b), as regnn_ns_gat_bwd's g_ft: hardware float atomics into a
+ * buffer ZERO-FILLED BY THE CALLER, ONE per element per entry (the score term q folded into the
+ * message's atomic: no more atomics than regnn_ns_gat_bwd issues), each wave-instruction 64
+ * consecutive columns of one source row (256 contiguous bytes).
+ *
+ * 1 <= H <= 16, C % 4 == 0, 4 <= C <= 512 and H * C <= 2048 (the lane's g_att accumulators stay
+ * in registers: REGNN_MAG_ATTN_MAX_WIDTH's bound), n_rel * H <= REGNN_NS_GAT_MAX_BINS with a
+ * tab_slab, slab_rows <= REGNN_NS_GAT_WORK_FLOATS, else REGNN_EUNSUPPORTED; a NULL required
+ * pointer (or tab without rel, tab_slab without tab, a slab with slab_rows < 1) REGNN_EINVAL;
+ * both before any launch. Added without an ABI bump (the version stays 51), as regnn_ns_gat_*:
+ * two new symbols only. */
+int regnn_ns_gatv2_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                       const float* xs, const float* xd, const float* att, const float* tab,
+                       float slope, int64_t cap_dst, int64_t n_src, int32_t H, int32_t C, float* a,
+                       float* out, float* work, hipStream_t stream);
+int regnn_ns_gatv2_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                       const float* xs, const float* xd, const float* att, const float* tab,
+                       const float* a, const float* gy, float slope, int64_t cap_dst,
+                       int64_t n_src, int32_t H, int32_t C, int32_t n_rel, float* g_xs,
+                       float* g_xd, float* att_slab, float* tab_slab, int32_t slab_rows,
+                       hipStream_t stream);
 
 /* Forward-only attention of the mag REGATConv / REGATv2Conv layers for the layer-wise
  * full-neighbour inference (mag/regnn_ns.py:348-369), in two calls.

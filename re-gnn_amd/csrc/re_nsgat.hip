@@ -11,34 +11,10 @@
 //                                   replayed graph needs no reset), den in entry order, a, out
 //   backward  ns_gat_bwd_kernel     ga, D, gs, gl per row; g_er and the relation slab in entry
 //                                   order; g_el / g_ft by float atomics (form (b), regnn_hip.h)
-#include "regnn_common.h"
-
-#include <math.h>
+#include "re_nsgat_common.h"
 
 namespace regnn {
 namespace {
-
-constexpr int kChunk = 64;                  // entries of a row held in LDS at a time
-constexpr int kMaxHeads = 16;
-constexpr int kWaves = kBlock / 64;
-
-// LDS written by some lanes of this wave, read by others: the wave's own LDS traffic in order
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ float wave_maxf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// an entry whose source id lies outside [0, n_src) takes no part: score -inf, weight 0
-__device__ __forceinline__ bool src_ok(int u, int64_t n_src) {
-    return u >= 0 && int64_t(u) < n_src;
-}
 
 __device__ __forceinline__ float pre_act(const float* __restrict__ el, const float* __restrict__ er,
                                          const float* __restrict__ tab, int u, int64_t v, int r,
@@ -53,7 +29,6 @@ ns_gat_score_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
                     const float* __restrict__ er, const float* __restrict__ tab, float slope,
                     int64_t n_rows, int64_t n_src, int H, float* __restrict__ s,
                     float* __restrict__ wgmax) {
-    __shared__ float smax[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float m = -INFINITY;
     for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
@@ -73,15 +48,7 @@ ns_gat_score_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
             s[int64_t(e) * H + h] = x;
         }
     }
-    m = wave_maxf(m);
-    if (lane == 0) smax[wave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float b = smax[0];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) b = fmaxf(b, smax[w]);
-        wgmax[blockIdx.x] = b;                 // every workgroup, every call
-    }
+    store_wg_max(m, wgmax);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -89,78 +56,7 @@ ns_gat_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
                   const float* __restrict__ ft, const float* __restrict__ wgmax, int n_wg,
                   int64_t n_rows, int64_t n_src, int H, int C, float* __restrict__ a,
                   float* __restrict__ out) {
-    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
-    __shared__ int su_[kWaves][kChunk];
-    __shared__ float sden_[kWaves][kMaxHeads];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* sa = sa_[wave];
-    int* su = su_[wave];
-    float* sden = sden_[wave];
-    float gmax = -INFINITY;
-    for (int i = lane; i < n_wg; i += 64) gmax = fmaxf(gmax, wgmax[i]);
-    gmax = wave_maxf(gmax);
-    const int HC = H * C, nvec = HC >> 2;
-    for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
-         v += int64_t(gridDim.x) * kWaves) {
-        const int e0 = ptr[v], e1 = ptr[v + 1];
-        float* orow = out + v * HC;
-        if (e1 <= e0) {                        // a padded row: exact zeros
-            for (int c = lane; c < nvec; c += 64)
-                *reinterpret_cast<float4*>(orow + 4 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        wave_lds_sync();                       // the previous row's reads of sden are done
-        if (lane < H) {                        // the row's denominators, in entry order
-            float den = 0.f;
-            for (int e = e0; e < e1; ++e) {
-                const float sv = a[int64_t(e) * H + lane];
-                den += sv == -INFINITY ? 0.f : expf(sv - gmax);
-            }
-            sden[lane] = den;
-        }
-        for (int t0 = 0; t0 < nvec; t0 += 64) {
-            const int c4 = t0 + lane;
-            const bool active = c4 < nvec;
-            const int h = active ? (4 * c4) / C : 0;
-            const bool last = t0 + 64 >= nvec;     // this pass replaces s by a in the buffer
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int cb = e0; cb < e1; cb += kChunk) {
-                const int nc = min(kChunk, e1 - cb);
-                wave_lds_sync();               // sden written; the previous chunk read
-                for (int i = lane; i < nc * H; i += 64) {
-                    const int j = i / H, hh = i - j * H;
-                    const int64_t at = int64_t(cb + j) * H + hh;
-                    // (rows wider than 64 vectors take several passes: all but the last leave s
-                    // in the buffer and form the same a from it again)
-                    const float sv = a[at];
-                    const float w = (sv == -INFINITY ? 0.f : expf(sv - gmax)) /
-                                    (sden[hh] + 1e-16f);
-                    if (last) a[at] = w;
-                    sa[i] = w;
-                }
-                for (int j = lane; j < nc; j += 64) {
-                    const int u = idx[cb + j];
-                    su[j] = src_ok(u, n_src) ? u : -1;
-                }
-                wave_lds_sync();
-                if (active) {
-#pragma unroll 4
-                    for (int j = 0; j < nc; ++j) {
-                        const int u = su[j];
-                        if (u < 0) continue;
-                        const float w = sa[j * H + h];
-                        const float4 x = *reinterpret_cast<const float4*>(
-                            ft + int64_t(u) * HC + 4 * c4);
-                        acc.x = fmaf(w, x.x, acc.x);
-                        acc.y = fmaf(w, x.y, acc.y);
-                        acc.z = fmaf(w, x.z, acc.z);
-                        acc.w = fmaf(w, x.w, acc.w);
-                    }
-                }
-            }
-            if (active) *reinterpret_cast<float4*>(orow + 4 * c4) = acc;
-        }
-    }
+    ns_softmax_aggregate(ptr, idx, ft, wgmax, n_wg, n_rows, n_src, H, C, a, out);
 }
 
 // One wave per row. Pass 1 over the row's chunks: ga[e,h] = <gy[v,h,:], ft[u,h,:]> (a lane per
@@ -289,16 +185,6 @@ ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
     }
 }
 
-inline int shape_rc(int32_t H, int32_t C) {
-    if (H < 1 || H > kMaxHeads || C < 4 || C > 512 || (C & 3)) return REGNN_EUNSUPPORTED;
-    return REGNN_OK;
-}
-
-inline int ns_gat_grid(int64_t cap_dst) {
-    const int64_t g = (cap_dst + kWaves - 1) / kWaves;
-    return int(g < 1 ? 1 : g < REGNN_NS_GAT_WORK_FLOATS ? g : REGNN_NS_GAT_WORK_FLOATS);
-}
-
 }  // namespace
 }  // namespace regnn
 
@@ -312,7 +198,7 @@ extern "C" int regnn_ns_gat_fwd(const int32_t* ptr, const int32_t* idx, const ui
     if (!ptr || !idx || !el || !er || !ft || !a || !out || !work || (tab && !rel) ||
         cap_dst < 0 || n_src < 0)
         return REGNN_EINVAL;
-    if (const int rc = shape_rc(H, C)) return rc;
+    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
     if (cap_dst == 0) return REGNN_OK;
     const int grid = ns_gat_grid(cap_dst);
     hipLaunchKernelGGL(ns_gat_score_kernel, dim3(grid), dim3(kBlock), 0, stream, ptr, idx, rel,
@@ -335,7 +221,7 @@ extern "C" int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const ui
         (tab && !rel) || (slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 ||
         (tab && n_rel < 1) || (slab && slab_rows < 1))
         return REGNN_EINVAL;
-    if (const int rc = shape_rc(H, C)) return rc;
+    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
     if (slab && (int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS || slab_rows > REGNN_NS_GAT_WORK_FLOATS))
         return REGNN_EUNSUPPORTED;
     if (cap_dst == 0 && !slab) return REGNN_OK;

@@ -1,0 +1,290 @@
+// mag REGATv2Conv attention over one device-sampled block as the sampler leaves it (regnn_ns_hop's
+// capacity-sized CSR, see re_nsgat.hip): mag/regnn_layers.py:399-413 with the softmax of
+// mag/utils.py:45-57 (ONE maximum over every live entry and head, + 1e-16 in the denominator).
+// xs is both the score operand and the message (lin_dst is lin_src, propagate sends x_src).
+//
+//   launch 1  ns_gatv2_score_kernel  s[e,h] = sum_d att[h,d] LeakyReLU(xs[u,h,d] + xd[v,h,d])
+//                                    + tab[rel_e,h] into the `a` buffer: a lane per (entry, head),
+//                                    d ascending in ONE fmaf chain from 0, the relation term added
+//                                    last; one maximum per workgroup
+//   launch 2  ns_gatv2_fwd_kernel    re_nsgat_common.h's softmax and aggregation (as ns_gat's)
+//   backward  ns_gatv2_bwd_kernel    ga, D, gs per row as ns_gat's; then a lane per column of the
+//                                    row: pre recomputed, g_xd and the workgroup's g_att partial
+//                                    in entry order in registers, the relation bins by lane h, and
+//                                    ONE float atomic per element per entry into g_xs (message
+//                                    and score terms folded; form (b), regnn_hip.h)
+#include "re_nsgat_common.h"
+
+namespace regnn {
+namespace {
+
+constexpr int kMaxWidth = 2048;             // H * C: <= 32 columns per lane, in registers
+
+__global__ void __launch_bounds__(kBlock)
+ns_gatv2_score_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                      const uint8_t* __restrict__ rel, const float* __restrict__ xs,
+                      const float* __restrict__ xd, const float* __restrict__ att,
+                      const float* __restrict__ tab, float slope, int64_t n_rows, int64_t n_src,
+                      int H, int C, float* __restrict__ s, float* __restrict__ wgmax) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int HC = H * C, nv = C >> 2;
+    float m = -INFINITY;
+    for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
+         v += int64_t(gridDim.x) * kWaves) {
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        const int n = (e1 - e0) * H;
+        for (int i = lane; i < n; i += 64) {
+            const int j = i / H, h = i - j * H;
+            const int e = e0 + j;
+            const int u = idx[e];
+            float x = -INFINITY;
+            if (src_ok(u, n_src)) {
+                const float4* xp = reinterpret_cast<const float4*>(xs + int64_t(u) * HC + h * C);
+                const float4* dp = reinterpret_cast<const float4*>(xd + v * HC + h * C);
+                const float4* ap = reinterpret_cast<const float4*>(att + h * C);
+                x = 0.f;
+                for (int c = 0; c < nv; ++c) {
+                    const float4 p = xp[c], q = dp[c], w = ap[c];
+                    const float p0 = p.x + q.x, p1 = p.y + q.y, p2 = p.z + q.z, p3 = p.w + q.w;
+                    x = fmaf(w.x, p0 > 0.f ? p0 : p0 * slope, x);
+                    x = fmaf(w.y, p1 > 0.f ? p1 : p1 * slope, x);
+                    x = fmaf(w.z, p2 > 0.f ? p2 : p2 * slope, x);
+                    x = fmaf(w.w, p3 > 0.f ? p3 : p3 * slope, x);
+                }
+                if (tab) x += tab[int(rel[e]) * H + h];
+                m = fmaxf(m, x);
+            }
+            s[int64_t(e) * H + h] = x;
+        }
+    }
+    store_wg_max(m, wgmax);
+}
+
+__global__ void __launch_bounds__(kBlock)
+ns_gatv2_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                    const float* __restrict__ xs, const float* __restrict__ wgmax, int n_wg,
+                    int64_t n_rows, int64_t n_src, int H, int C, float* __restrict__ a,
+                    float* __restrict__ out) {
+    ns_softmax_aggregate(ptr, idx, xs, wgmax, n_wg, n_rows, n_src, H, C, a, out);
+}
+
+// One wave per row, T = the columns per lane (column lane + 64 t of the row's H*C, t < T).
+// Pass 1 over the row's chunks: ga[e,h] = <gy[v,h,:], xs[u,h,:]> (a lane per (entry, head),
+// columns in order) and D[v,h] = sum a ga in entry order. Pass 2: gs = a (ga - D) into LDS, the
+// wave's relation bins by lane h in entry order, then per column: pre = xs[u] + xd[v] again,
+// q = gs att LeakyReLU'(pre), g_xd and g_att += in entry order, and the one atomic a gy + q into
+// g_xs -- one instruction per 64 consecutive columns of a source row (256 contiguous bytes). A row
+// of more than one chunk recomputes ga in pass 2 (the same instructions on the same operands: the
+// same bits) and carries its g_xd sums from chunk to chunk through the row it writes (the lane's
+// own stores: still one chain in entry order).
+template <int T>
+__global__ void __launch_bounds__(kBlock)
+ns_gatv2_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                    const uint8_t* __restrict__ rel, const float* __restrict__ xs,
+                    const float* __restrict__ xd, const float* __restrict__ att,
+                    const float* __restrict__ tab, const float* __restrict__ a,
+                    const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src,
+                    int H, int C, int n_rel, float* __restrict__ g_xs, float* __restrict__ g_xd,
+                    float* __restrict__ att_slab, float* __restrict__ tab_slab) {
+    extern __shared__ float dyn_[];            // [kWaves][n_rel * H] when tab_slab, then [H * C]
+    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
+    __shared__ float sg_[kWaves][kChunk * kMaxHeads];
+    __shared__ int su_[kWaves][kChunk];
+    __shared__ int sr_[kWaves][kChunk];
+    __shared__ float sD_[kWaves][kMaxHeads];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* sa = sa_[wave];
+    float* sg = sg_[wave];
+    int* su = su_[wave];
+    int* sr = sr_[wave];
+    float* sD = sD_[wave];
+    const int W = tab_slab ? n_rel * H : 0;
+    float* bins = dyn_ + wave * W;
+    float* attred = dyn_ + kWaves * W;
+    if (tab_slab) {
+        for (int i = threadIdx.x; i < kWaves * W; i += kBlock) dyn_[i] = 0.f;
+        __syncthreads();
+    }
+    const int HC = H * C;
+    float gatt[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) gatt[t] = 0.f;
+    for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
+         v += int64_t(gridDim.x) * kWaves) {
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        float* gxdr = g_xd + v * HC;
+        if (e1 <= e0) {
+            for (int c = lane; c < (HC >> 2); c += 64)
+                *reinterpret_cast<float4*>(gxdr + 4 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const float* gyr = gy + v * HC;
+        const float* xdr = xd + v * HC;
+        // the chunk [cb, cb + nc): ids, a and ga into LDS
+        auto fill = [&](int cb, int nc) {
+            wave_lds_sync();
+            for (int j = lane; j < nc; j += 64) {
+                const int u = idx[cb + j];
+                su[j] = src_ok(u, n_src) ? u : -1;
+                sr[j] = tab ? int(rel[cb + j]) : 0;
+            }
+            for (int i = lane; i < nc * H; i += 64) {
+                const int j = i / H, hh = i - j * H;
+                const int u = idx[cb + j];
+                float d = 0.f, w = 0.f;
+                if (src_ok(u, n_src)) {
+                    w = a[int64_t(cb + j) * H + hh];
+                    const float4* gp = reinterpret_cast<const float4*>(gyr + hh * C);
+                    const float4* xp = reinterpret_cast<const float4*>(
+                        xs + int64_t(u) * HC + hh * C);
+                    for (int c = 0; c < (C >> 2); ++c) {
+                        const float4 g = gp[c], x = xp[c];
+                        d = fmaf(g.x, x.x, d);
+                        d = fmaf(g.y, x.y, d);
+                        d = fmaf(g.z, x.z, d);
+                        d = fmaf(g.w, x.w, d);
+                    }
+                }
+                sa[i] = w;
+                sg[i] = d;
+            }
+            wave_lds_sync();
+        };
+        const bool one = e1 - e0 <= kChunk;
+        float D = 0.f;
+        for (int cb = e0; cb < e1; cb += kChunk) {
+            const int nc = min(kChunk, e1 - cb);
+            fill(cb, nc);
+            if (lane < H)
+                for (int j = 0; j < nc; ++j) D = fmaf(sa[j * H + lane], sg[j * H + lane], D);
+        }
+        if (lane < H) sD[lane] = D;
+        for (int cb = e0; cb < e1; cb += kChunk) {
+            const int nc = min(kChunk, e1 - cb);
+            if (!one) fill(cb, nc);
+            else wave_lds_sync();              // sD written
+            for (int i = lane; i < nc * H; i += 64) {
+                const int hh = i % H;
+                sg[i] = sa[i] * (sg[i] - sD[hh]);      // gs (this lane's own slot; 0 where a is)
+            }
+            wave_lds_sync();
+            if (tab_slab && lane < H) {
+                for (int j = 0; j < nc; ++j) {
+                    const int r = sr[j];
+                    if (su[j] >= 0 && r < n_rel) bins[r * H + lane] += sg[j * H + lane];
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int col = lane + 64 * t;
+                if (col >= HC) continue;
+                const int h = col / C;
+                const float g = gyr[col], dv = xdr[col], w = att[col];
+                float gd = cb == e0 ? 0.f : gxdr[col];
+                float ga = gatt[t];
+                for (int j = 0; j < nc; ++j) {
+                    const int u = su[j];
+                    if (u < 0) continue;
+                    float* dst = g_xs + int64_t(u) * HC + col;
+                    const float pre = xs[int64_t(u) * HC + col] + dv;
+                    const float gs = sg[j * H + h];
+                    const float q = gs * w * (pre > 0.f ? 1.f : slope);
+                    gd += q;
+                    ga = fmaf(gs, pre > 0.f ? pre : pre * slope, ga);
+                    unsafeAtomicAdd(dst, fmaf(sa[j * H + h], g, q));
+                }
+                gxdr[col] = gd;
+                gatt[t] = ga;
+            }
+        }
+    }
+    if (tab_slab) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < W; i += kBlock) {
+            float t = dyn_[i];                 // the waves' bins in wave order
+#pragma unroll
+            for (int w = 1; w < kWaves; ++w) t += dyn_[w * W + i];
+            tab_slab[int64_t(blockIdx.x) * W + i] = t;
+        }
+    }
+    if (!att_slab) return;
+    for (int w = 0; w < kWaves; ++w) {         // the waves' g_att partials in wave order
+        if (wave == w) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int col = lane + 64 * t;
+                if (col < HC) attred[col] = w ? attred[col] + gatt[t] : gatt[t];
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < HC; i += kBlock)
+        att_slab[int64_t(blockIdx.x) * HC + i] = attred[i];
+}
+
+inline int ns_gatv2_shape_rc(int32_t H, int32_t C) {
+    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
+    return H * C > kMaxWidth ? REGNN_EUNSUPPORTED : REGNN_OK;
+}
+
+}  // namespace
+}  // namespace regnn
+
+using namespace regnn;
+
+extern "C" int regnn_ns_gatv2_fwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                                  const float* xs, const float* xd, const float* att,
+                                  const float* tab, float slope, int64_t cap_dst, int64_t n_src,
+                                  int32_t H, int32_t C, float* a, float* out, float* work,
+                                  hipStream_t stream) {
+    if (!ptr || !idx || !xs || !xd || !att || !a || !out || !work || (tab && !rel) ||
+        cap_dst < 0 || n_src < 0)
+        return REGNN_EINVAL;
+    if (const int rc = ns_gatv2_shape_rc(H, C)) return rc;
+    if (cap_dst == 0) return REGNN_OK;
+    const int grid = ns_gat_grid(cap_dst);
+    hipLaunchKernelGGL(ns_gatv2_score_kernel, dim3(grid), dim3(kBlock), 0, stream, ptr, idx, rel,
+                       xs, xd, att, tab, slope, cap_dst, n_src, int(H), int(C), a, work);
+    REGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ns_gatv2_fwd_kernel, dim3(grid), dim3(kBlock), 0, stream, ptr, idx, xs,
+                       static_cast<const float*>(work), grid, cap_dst, n_src, int(H), int(C), a,
+                       out);
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}
+
+extern "C" int regnn_ns_gatv2_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                                  const float* xs, const float* xd, const float* att,
+                                  const float* tab, const float* a, const float* gy, float slope,
+                                  int64_t cap_dst, int64_t n_src, int32_t H, int32_t C,
+                                  int32_t n_rel, float* g_xs, float* g_xd, float* att_slab,
+                                  float* tab_slab, int32_t slab_rows, hipStream_t stream) {
+    const bool slabs = att_slab || tab_slab;
+    if (!ptr || !idx || !xs || !xd || !att || !a || !gy || !g_xs || !g_xd || (tab && !rel) ||
+        (tab_slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) ||
+        (slabs && slab_rows < 1))
+        return REGNN_EINVAL;
+    if (const int rc = ns_gatv2_shape_rc(H, C)) return rc;
+    if ((tab_slab && int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS) ||
+        (slabs && slab_rows > REGNN_NS_GAT_WORK_FLOATS))
+        return REGNN_EUNSUPPORTED;
+    if (cap_dst == 0 && !slabs) return REGNN_OK;
+    // with a slab the launch has exactly slab_rows workgroups: each writes its rows
+    const int grid = slabs ? int(slab_rows) : ns_gat_grid(cap_dst);
+    const int HC = H * C;
+    const size_t lds = ((tab_slab ? size_t(kWaves) * n_rel * H : 0) + (att_slab ? HC : 0)) *
+                       sizeof(float);
+#define REGNN_NS_GATV2_BWD(T)                                                                    \
+    hipLaunchKernelGGL(ns_gatv2_bwd_kernel<T>, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,  \
+                       rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, int(H), int(C),      \
+                       int(n_rel), g_xs, g_xd, att_slab, tab_slab)
+    if (HC <= 64) REGNN_NS_GATV2_BWD(1);
+    else if (HC <= 128) REGNN_NS_GATV2_BWD(2);
+    else if (HC <= 256) REGNN_NS_GATV2_BWD(4);
+    else if (HC <= 512) REGNN_NS_GATV2_BWD(8);
+    else if (HC <= 1024) REGNN_NS_GATV2_BWD(16);
+    else REGNN_NS_GATV2_BWD(32);
+#undef REGNN_NS_GATV2_BWD
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}

@@ -118,6 +118,10 @@ _SIG = {
     "regnn_ns_gat_fwd": ([P, P, P, P, P, P, P, F32, I64, I64, I32, I32, P, P, P, P], ctypes.c_int),
     "regnn_ns_gat_bwd": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P,
                           I32, P], ctypes.c_int),
+    "regnn_ns_gatv2_fwd": ([P, P, P, P, P, P, P, F32, I64, I64, I32, I32, P, P, P, P],
+                           ctypes.c_int),
+    "regnn_ns_gatv2_bwd": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P,
+                            I32, P], ctypes.c_int),
     "regnn_mag_attn_fwd": ([P, P, P, P, I32, P, P, P, P, P, P, P, P, I64, I32, I32, F32, P, P],
                            ctypes.c_int),
     "regnn_mag_attn_epilogue": ([P, P, P, P, F32, P, P, P, P, F32, I32, I64, I32, I32, P, P],

@@ -300,7 +300,9 @@ class REGATConv(torch.nn.Module):
 
 class REGATv2Conv(REGATConv):
     """mag/regnn_layers.py:318-436: score <att, LeakyReLU(x_src[u] + x_dst[v])> + rw[type] (HIP
-    GATv2 SDDMM, regnn_gatv2_score_*), the same global-max softmax (regnn_edge_softmax_*)."""
+    GATv2 SDDMM, regnn_gatv2_score_*), the same global-max softmax (regnn_edge_softmax_*). On a
+    device-sampled NSBlock, with GATV2_BLOCKS on, all of it is ops.ns_gatv2 (regnn_ns_gatv2_fwd /
+    _bwd); with the knob off (the default) a block is refused."""
 
     v2 = True
 
@@ -311,15 +313,30 @@ class REGATv2Conv(REGATConv):
         init.xavier_uniform_(self.att)
 
     def _block_attention(self, blk, x_src, x_dst, tab, n_dst, return_weights):
-        raise NotImplementedError("REGATv2Conv does not run on device-sampled blocks (ops.ns_gat "
-                                  "covers REGATConv's scores only): pass the exact-size "
-                                  "edge_index / edge_type adjs")
+        """out [n_dst, H, C] over a device-sampled NSBlock: ops.ns_gatv2, with GATV2_BLOCKS on"""
+        if GATV2_BLOCKS["mode"] != "on":
+            raise NotImplementedError(
+                "REGATv2Conv does not run on device-sampled blocks (ops.ns_gat covers REGATConv's "
+                "scores only): pass the exact-size edge_index / edge_type adjs")
+        if return_weights:
+            raise ValueError("return_weights needs the edge_index / edge_type tensors, not a "
+                             "device-sampled block")
+        if self.self_loop_type != 2:
+            raise ValueError("a device-sampled block holds self_loop_type 2's self loops; this "
+                             f"conv has self_loop_type {self.self_loop_type}")
+        if blk.n_dst != n_dst:
+            raise ValueError(f"the block has {blk.n_dst} target rows, x_target {n_dst}")
+        return ops.ns_gatv2(blk, x_src, x_dst, self.att, tab, self.negative_slope)   # :399-417
 
     def _attention(self, rg, pack, x_src, x_dst, tab):
         s = ops.gatv2_scores(rg, x_src, x_dst, self.att, self.negative_slope)  # :399-404
         return ops.edge_softmax_logits(rg, s, tab, pack, global_max=True)     # :407-413
 
 
+# "on": REGATv2Conv runs on a device-sampled NSBlock through ops.ns_gatv2 (regnn_ns_gatv2_fwd /
+# _bwd), and NSTrainer(device_blocks=True) takes 'regatv2' models; "off" (the default): the conv
+# refuses a block and 'regatv2' trains on the exact-size path, as before the operator existed
+GATV2_BLOCKS = {"mode": os.environ.get("REGNN_GATV2_BLOCKS", "off")}
 # "auto": layer 0 of a device-block REGNN (regcn, self-loop type 2, feats_type 3) aggregates the
 # raw input rows per node type and projects after (REGNN._typed_first_layer); "off": group_input
 # over every sampled node first, as the reference orders it (tests compare the two)
@@ -631,12 +648,15 @@ class REGNN(torch.nn.Module):
                 x = self.convs[i].forward_act(x, x_target, blk, ep[0], ep[1], i,
                                               tab=None if tabs is None else tabs[i])
                 continue                       # (relu and dropout applied in the epilogue)
-            # (regat: REGATConv's attention over the block, ops.ns_gat -- only where the adj IS
-            # the block, NSTrainer(device_blocks=True); a PyG-style Adj carrying one keeps the
-            # exact-size path)
+            # (regat: REGATConv's attention over the block, ops.ns_gat; regatv2 with GATV2_BLOCKS
+            # on: ops.ns_gatv2 -- only where the adj IS the block,
+            # NSTrainer(device_blocks=True); a PyG-style Adj carrying one keeps the exact-size
+            # path)
             if (blk is not None and self.self_loop_type == 2 and
                     (self.model == 'regcn' or
-                     (self.model == 'regat' and blk is edge_index))):
+                     (self.model == 'regat' and blk is edge_index) or
+                     (self.model == 'regatv2' and blk is edge_index and
+                      GATV2_BLOCKS["mode"] == "on"))):
                 x = self.convs[i]((x, x_target), blk)          # relation ids formed on device
                 x = F.relu(x)
                 x = F.dropout(x, p=self.dropout, training=self.training)

@@ -470,13 +470,17 @@ def gat_blocks_unsupported(model, x_dict):
     """why NSTrainer(device_blocks=True) cannot train this model on the sampler's capacity-sized
     blocks (None: it can). Covered: mag.REGNN 'regat' (REGATConv over ops.ns_gat) with
     self_loop_type 2 (the self loops the sampler writes), use_norm 'ln' or none, fp32 tables,
-    1..16 heads and a head width that is a multiple of 4 in [4, 512]."""
+    1..16 heads and a head width that is a multiple of 4 in [4, 512]; and, with
+    mag.GATV2_BLOCKS on, 'regatv2' (REGATv2Conv over ops.ns_gatv2) under the same conditions
+    and heads x head width <= 2048."""
+    from . import mag, ops
     kind = getattr(model, "model", None)
-    if kind == "regatv2":
+    if kind == "regatv2" and mag.GATV2_BLOCKS["mode"] != "on":
         return ("regatv2: GATv2 scores have no device-block operator (ops.ns_gat covers "
                 "REGATConv only); it stays on the exact-size path")
-    if kind != "regat":
+    if kind not in ("regat", "regatv2"):
         return f"model {kind!r} is neither 'regcn' nor 'regat'"
+    op = "ops.ns_gat" if kind == "regat" else "ops.ns_gatv2"
     if getattr(model, "self_loop_type", None) != 2:
         return (f"self_loop_type {getattr(model, 'self_loop_type', None)}: the sampler's blocks "
                 "carry self_loop_type 2's self loops (relation num_edge_types + node type)")
@@ -487,10 +491,13 @@ def gat_blocks_unsupported(model, x_dict):
         if c.use_norm not in ("ln", "non", None):
             return f"use_norm {c.use_norm!r}"
         if not (1 <= c.heads <= 16 and c.out_channels % 4 == 0 and 4 <= c.out_channels <= 512):
-            return (f"{c.heads} heads x {c.out_channels}: ops.ns_gat takes 1..16 heads and a "
+            return (f"{c.heads} heads x {c.out_channels}: {op} takes 1..16 heads and a "
                     "head width that is a multiple of 4 in [4, 512]")
+        if kind == "regatv2" and c.heads * c.out_channels > ops.NS_GATV2_MAX_WIDTH:
+            return (f"{c.heads} heads x {c.out_channels}: ops.ns_gatv2 takes heads x head width "
+                    f"<= {ops.NS_GATV2_MAX_WIDTH}")
     if any(torch.is_tensor(x) and x.dtype != torch.float32 for x in x_dict.values()):
-        return "the attention path reads fp32 input tables (no bf16 tables for 'regat')"
+        return f"the attention path reads fp32 input tables (no bf16 tables for {kind!r})"
     return None
 
 
@@ -1173,8 +1180,11 @@ class NSTrainer:
                  shuffle=True, engine="auto", adam=None, pipeline=True, device_blocks=False):
         """device_blocks: also hand mag 'regat' models the capacity-sized device blocks
         (REGATConv over ops.ns_gat: no host sync, pipelined, capturable) instead of the
-        exact-size adjs; raises ValueError where the blocks do not cover the model
-        (gat_blocks_unsupported). 'regcn' / self_loop_type 2 is on the blocks either way."""
+        exact-size adjs, and 'regatv2' models too where mag.GATV2_BLOCKS is on (REGATv2Conv
+        over ops.ns_gatv2, the same step: CSR hops, lookahead 1, two slots, one-step graphs);
+        raises ValueError where the blocks do not cover the model (gat_blocks_unsupported:
+        'regatv2' with the knob off among them). 'regcn' / self_loop_type 2 is on the blocks
+        either way."""
         self.model, self.opt = model, opt
         dev = rg.device
         self.device, self.rank, self.world = dev, int(rank), int(world)
@@ -1193,7 +1203,8 @@ class NSTrainer:
         # per step)
         self._blocks_ok = (getattr(model, "model", None) == "regcn" and
                            getattr(model, "self_loop_type", None) == 2)
-        # device_blocks: 'regat' too (mag.REGATConv reads the CSR blocks through ops.ns_gat);
+        # device_blocks: 'regat' too (mag.REGATConv reads the CSR blocks through ops.ns_gat), and
+        # 'regatv2' with mag.GATV2_BLOCKS on (mag.REGATv2Conv through ops.ns_gatv2);
         # refused with a reason where the blocks do not apply (never a silent fall-back)
         self._gat_blocks = False
         if device_blocks and not self._blocks_ok:
@@ -1285,8 +1296,8 @@ class NSTrainer:
         # the sampling lookahead (fused engine: default_ahead; the module path: MODULE_AHEAD)
         self.ahead = 1
         if self.pipelined:
-            # 'regat' on device blocks: lookahead 1 whatever MODULE_AHEAD says (two slots,
-            # one-step graphs only: every captured graph keeps a private pool of activations,
+            # 'regat' / 'regatv2' on device blocks: lookahead 1 whatever MODULE_AHEAD says (two
+            # slots, one-step graphs only: every captured graph keeps a private pool of activations,
             # 573 MB per [cap_src, 512] tensor at 8 heads x 64, batch 512, fan-out [25, 20])
             self.ahead = max(1, int(default_ahead(self.world) if self.fused is not None
                                     else 1 if self._gat_blocks else MODULE_AHEAD["n"]))

@@ -765,6 +765,105 @@ def ns_gat(blk, el, er, tab, ft, slope=0.2, return_attn=False):
     return (out, a) if return_attn else out
 
 
+NS_GATV2_MAX_WIDTH = 2048        # heads x head width of regnn_ns_gatv2_* (include/regnn_hip.h)
+
+
+def ns_gatv2_bytes(E, n_dst, H, C, kind):
+    """algorithmic HBM bytes of the sampled-block GATv2 attention: per entry its id, relation, a
+    (the score written, then read and replaced) and the source row, gathered twice each way (the
+    forward: for the score and for the message; the backward: for ga and for the recomputed
+    pre-activation) plus the backward's atomic row into g_xs; per target its ptr and the xd and
+    out rows (the backward: xd, gy and g_xd)."""
+    if kind == "fwd":
+        return E * (5 + 12 * H + 8 * H * C) + n_dst * (4 + 8 * H * C)
+    return E * (5 + 4 * H + 12 * H * C) + n_dst * (4 + 12 * H * C)
+
+
+class _NsGatv2(torch.autograd.Function):
+    """(out, a) of regnn_ns_gatv2_fwd over a device-sampled block in the CSR layout; backward
+    regnn_ns_gatv2_bwd (+ regnn_rel_reduce for att and the relation table). a is not
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, xs, xd, att, tab, blk, slope):
+        for name, t in (("xs", xs), ("xd", xd), ("att", att), ("tab", tab)):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError(f"ns_gatv2: {name} is {t.dtype}; the sampled-block attention "
+                                "runs on fp32")
+        if getattr(blk, "strided_rows", None) is not None:
+            raise ValueError("ns_gatv2 reads the CSR layout; this block was sampled in the "
+                             "fixed-stride layout (strided_rows)")
+        if xs.dim() != 3 or xd.dim() != 3:
+            raise ValueError("ns_gatv2: xs [n, H, C], xd [n_dst, H, C]")
+        H, C = int(xs.shape[1]), int(xs.shape[2])
+        if (tuple(xd.shape) != (blk.n_dst, H, C) or att.numel() != H * C or
+                tuple(att.shape[-2:]) != (H, C) or
+                (tab is not None and (tab.dim() != 2 or tab.shape[1] != H))):
+            raise ValueError(f"ns_gatv2: xs {tuple(xs.shape)}, xd {tuple(xd.shape)}, att "
+                             f"{tuple(att.shape)} do not fit a block of {blk.n_dst} targets")
+        xs, xd, w = xs.contiguous(), xd.contiguous(), att.detach().contiguous()
+        t = None if tab is None else tab.detach().contiguous()
+        n_src = min(int(xs.shape[0]), blk.n_src)
+        a = torch.empty(blk.csr_idx.numel(), H, dtype=torch.float32, device=xs.device)
+        out = torch.empty(blk.n_dst, H, C, dtype=torch.float32, device=xs.device)
+        work = torch.empty(NS_GAT_WORK_FLOATS, dtype=torch.float32, device=xs.device)
+        with timed("ns_gatv2_fwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "fwd")):
+            L.call("regnn_ns_gatv2_fwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+                   L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
+                   L.ptr(t), float(slope), blk.n_dst, n_src, H, C, L.ptr(a), L.ptr(out),
+                   L.ptr(work), L.stream())
+        ctx.blk, ctx.slope, ctx.n_src = blk, float(slope), n_src
+        ctx.att_shape = att.shape
+        ctx.tab_shape = None if tab is None else tab.shape
+        ctx.save_for_backward(xs, xd, w, t, a)
+        ctx.mark_non_differentiable(a)
+        return out, a
+
+    @staticmethod
+    def backward(ctx, gy, _ga):
+        xs, xd, w, t, a = ctx.saved_tensors
+        blk = ctx.blk
+        H, C = int(xs.shape[1]), int(xs.shape[2])
+        gy = gy.contiguous().float()
+        g_xs = torch.zeros_like(xs)                                  # the atomics' target
+        g_xd = torch.empty_like(xd)
+        n_rel = int(t.shape[0]) if t is not None else 0
+        need_att = ctx.needs_input_grad[2]
+        need_tab = t is not None and ctx.needs_input_grad[3]
+        att_slab = tab_slab = None
+        rows = 0
+        if need_att or need_tab:
+            rows = max(1, min(NS_GAT_BWD_ROWS["n"], NS_GAT_WORK_FLOATS, -(-blk.n_dst // 4)))
+            if need_att:
+                att_slab = torch.empty(rows, H * C, dtype=torch.float32, device=xs.device)
+            if need_tab:
+                tab_slab = torch.empty(rows, n_rel * H, dtype=torch.float32, device=xs.device)
+        with timed("ns_gatv2_bwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "bwd")):
+            L.call("regnn_ns_gatv2_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+                   L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
+                   L.ptr(t), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C, n_rel,
+                   L.ptr(g_xs), L.ptr(g_xd), L.ptr(att_slab), L.ptr(tab_slab), rows, L.stream())
+        g_att = _reduce(att_slab, H * C).view(ctx.att_shape) if need_att else None
+        g_tab = _reduce(tab_slab, n_rel * H).view(ctx.tab_shape) if need_tab else None
+        return g_xs, g_xd, g_att, g_tab, None, None
+
+
+def ns_gatv2(blk, xs, xd, att, tab, slope=0.2, return_attn=False):
+    """mag REGATv2Conv's attention and aggregation over a device-sampled block as the sampler
+    leaves it (regnn_hip.ns.NSBlock in the CSR layout, capacity-sized, no host size):
+    out[v,h,:] = sum_e a[e,h] xs[idx_e,h,:], a = the ogbn-mag softmax (one global maximum,
+    + 1e-16, mag/utils.py:45-57) of sum_d att[h,d] LeakyReLU(xs[idx_e,h,d] + xd[v,h,d], slope)
+    + tab[rel_e,h] (mag/regnn_layers.py:399-413). xs [>= blk.n_src, H, C] holds the block's
+    source rows, score operand and message at once (rows past the sampled ones unread, their
+    gradients zero), xd [blk.n_dst, H, C] the target rows, att [H, C] (or [1, H, C]), tab
+    [n_rel, H] or None; rows of out past the batch's live targets are zeros. H in 1..16, C a
+    multiple of 4 in [4, 512], H * C <= 2048. The backward is the global-max softmax's with the
+    maximum a constant; g_xd, g_att and g_tab are summed in a fixed order, g_xs by float atomics
+    (regnn_ns_gatv2_bwd). return_attn: also a [blk capacity entries, H] (no gradient)."""
+    out, a = _NsGatv2.apply(xs, xd, att, tab, blk, slope)
+    return (out, a) if return_attn else out
+
+
 
 class _NsTypedAgg(torch.autograd.Function):
     """S[v, t] = sum_{e in v, type(src) = t} tab[rel_e] x_src (raw input rows read through n_id /

@@ -1,7 +1,8 @@
-"""Per-step time of NS 'regat' training on the device-sampled blocks against the default
-exact-size path, in one process (bench.py times the 'regcn' step only):
+"""Per-step time of NS 'regat' / 'regatv2' training on the device-sampled blocks against the
+default exact-size path, in one process (bench.py times the 'regcn' step only):
 
-    python tools/ns_gat_time.py [--scale 1] [--batch 512] [--steps 20] [--rounds 7] [--out FILE]
+    python tools/ns_gat_time.py [--model regat] [--scale 1] [--batch 512] [--steps 20]
+                                [--rounds 7] [--kernel-steps 0] [--out FILE]
 
 One graph -- mag_like(scale), 128-d inputs, REGNN 'regat' hidden 64 x 8 heads, 349 classes,
 fan-out [25, 20], dropout 0.5, FlatAdam -- and two trainers over it:
@@ -12,6 +13,11 @@ fan-out [25, 20], dropout 0.5, FlatAdam -- and two trainers over it:
   B  NSTrainer(..., device_blocks=True)   the capacity-sized blocks through ops.ns_gat, the next
                                           batch sampled on a second stream, captured (one-step
                                           graphs), run_steps
+
+--model regatv2: the same two paths for REGATv2Conv; B switches mag.GATV2_BLOCKS on (the blocks
+through ops.ns_gatv2), A is the gatv2_scores / amax / edge_softmax / head SpMM chain.
+--kernel-steps K > 0: after the windows, K more eager steps of B under ops' event timers; the
+attention operator's device time per step (both layers) goes into "kernel_us_per_step".
 
 After warm-up runs of both, `rounds` timed windows of `steps` steps each, alternating A and B; a
 window is a host clock around the steps ending in a device synchronise. Prints (and with --out
@@ -44,6 +50,8 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--model", choices=["regat", "regatv2"], default="regat")
+    ap.add_argument("--kernel-steps", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -72,7 +80,7 @@ def main():
         torch.manual_seed(3)
         model = mag.REGNN(128, args.hidden, 349, 2, 10.0, args.dropout,
                           {k: 128 for k in x_dict}, 7, use_norm="ln", self_loop_type=2,
-                          model="regat", heads=args.heads).to(dev)
+                          model=args.model, heads=args.heads).to(dev)
         model.train()
         return NSTrainer(model, None, rg, [25, 20], args.batch,
                          torch.arange(n_paper, device=dev), x_dict, edge_type, node_type, local,
@@ -88,6 +96,8 @@ def main():
     torch.cuda.synchronize()
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
+    if args.model == "regatv2":
+        mag.GATV2_BLOCKS["mode"] = "on"        # path B only: A was built and warmed before
     tr_b = trainer(device_blocks=True)
     assert tr_b._gat_blocks and tr_b.pipelined and tr_b.ahead == 1
     tr_b.capture(warmup=2)
@@ -103,7 +113,7 @@ def main():
             run(args.steps)
             torch.cuda.synchronize()
             us[k].append((time.perf_counter() - t0) / args.steps * 1e6)
-    out = {"workload": f"mag_like({args.scale:g}) NS step, regat hidden {args.hidden} x "
+    out = {"workload": f"mag_like({args.scale:g}) NS step, {args.model} hidden {args.hidden} x "
                        f"{args.heads} heads, batch {args.batch}, fan-out [25, 20], dropout "
                        f"{args.dropout}, FlatAdam",
            "steps_per_window": args.steps, "rounds": args.rounds,
@@ -112,6 +122,16 @@ def main():
         out[k] = {"us_per_step_median": round(statistics.median(v), 1),
                   "min": round(min(v), 1), "max": round(max(v), 1),
                   "final_loss": float((tr_a if k == "exact_eager" else tr_b).loss)}
+    if args.kernel_steps > 0:
+        from regnn_hip import profile
+        profile.enable()
+        for _ in range(args.kernel_steps):
+            tr_b.step()
+        torch.cuda.synchronize()
+        out["kernel_us_per_step"] = {
+            k: round(v[2] * 1e3 / args.kernel_steps, 1)
+            for k, v in sorted(profile.summary().items()) if k.startswith("ns_gat")}
+        profile.enable(False)
     line = json.dumps(out)
     print(line)
     if args.out:
