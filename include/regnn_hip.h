@@ -849,8 +849,9 @@ int regnn_ns_spmm_bwd_csc(const int32_t* csc_ptr, const int32_t* csc_ent, const 
  * no transposed index, and one form keeps one kernel; the same documented exception as
  * regnn_ns_spmm_bwd (the summation order is run-dependent). Each g_ft atomic wave-instruction adds
  * 64 consecutive columns of one source row (256 contiguous bytes). Rows u the block never names
- * (u >= sizes[hop + 1]) keep the caller's zeros. A gather over hop 0's transposed index (form (a))
- * is not built.
+ * (u >= sizes[hop + 1]) keep the caller's zeros. Form (a), a gather over the block's transposed
+ * index with no atomics and no zero fill, is regnn_ns_block_tidx + regnn_ns_gat_bwd_gather /
+ * regnn_ns_gatv2_bwd_gather (below).
  *
  * 1 <= H <= 16, C % 4 == 0, 4 <= C <= 512, else REGNN_EUNSUPPORTED; a NULL required pointer (or
  * tab without rel, slab without tab) REGNN_EINVAL; both before any launch.
@@ -926,6 +927,88 @@ int regnn_ns_gatv2_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* re
                        int64_t n_src, int32_t H, int32_t C, int32_t n_rel, float* g_xs,
                        float* g_xd, float* att_slab, float* tab_slab, int32_t slab_rows,
                        hipStream_t stream);
+
+/* The canonical transposed index of one device-sampled CSR block, read exactly as regnn_ns_gat_*
+ * read it: ptr [cap_dst + 1], idx [cap_e], no host size, no blk.row. An entry e is live when it
+ * lies in [ptr[v], ptr[v + 1]) for some row v < cap_dst and 0 <= idx[e] < n_src (n_src <= cap_src).
+ *   t_ptr [cap_src + 1]  source u's live entries are the slots [t_ptr[u], t_ptr[u + 1]); a source
+ *                        nothing names has an empty segment; t_ptr[cap_src] = the live entries
+ *   t_pos [cap_e]        each slot's CSR position e, ASCENDING inside every segment: the stable
+ *                        sort of the live entries by source
+ *   t_row [cap_e]        each slot's target row v
+ *   t_long [regnn_ns_tidx_long_ints(cap_e)]  the long segments (more than REGNN_NS_TIDX_CHUNK
+ *                        entries) cut into pieces: t_long[0] = pieces, t_long[1] = long rows,
+ *                        t_long[2] = REGNN_NS_TIDX_CHUNK, t_long[3] = 0, then per piece four ints
+ *                        (source, first slot, count <= CHUNK, piece number << 16 | pieces of the
+ *                        row); sources ascending, a row's pieces consecutive (as csc_long's piece
+ *                        table). At most 2 (cap_e / CHUNK) + 2 pieces: the bound is from the
+ *                        capacity alone and is checked before any launch.
+ *   work [regnn_ns_tidx_work_ints(cap_src, cap_e)]  the build's scratch (counts / cursors, the
+ *                        slots as placed, the scan's tile sums), cleared by the build itself
+ * The output is a pure function of the block (a second call gives the same bits), every slot a
+ * reader takes is rewritten by every call (a replayed graph needs no reset), there is no host
+ * sync and every grid is sized by a capacity (capturable), and no workgroup waits on another: a
+ * clear and six launches -- counts by integer atomics (order-free); their exclusive scan over
+ * tiles of 1024 sources in three launches (the tiles' sums, ONE workgroup scanning those, each
+ * tile again with its offset: t_ptr, the cursors back to zero, the pieces); placement by an atomic
+ * cursor into the scratch; then a thread per slot ranking its position among its segment's (a
+ * count: order-free) and writing the entry at that rank. REGNN_NS_TIDX_CHUNK = 256: a piece is walked by one wave in slot order, and
+ * 256 slots of an 8 x 64 row are 512 KB of gathered gy rows per wave -- long enough to amortise
+ * the piece's partial row, short enough that a 500-entry hub spreads over several waves.
+ * A NULL pointer, a negative size or n_src > cap_src: REGNN_EINVAL. A capacity above 2^31 - 2,
+ * cap_e / CHUNK + 1 > 65535 (the piece word's 16-bit fields), or long_ints / work_ints below the
+ * query functions' values: REGNN_EUNSUPPORTED. Both before any launch.
+ *
+ * regnn_ns_gat_bwd_gather / regnn_ns_gatv2_bwd_gather: regnn_ns_gat_bwd / regnn_ns_gatv2_bwd
+ * with the per-source sums in form (a). The arguments of the atomic form, then the index, its
+ * capacities (cap_src: the index's rows; n_out: the rows of g_ft / g_el / g_xs, all written;
+ * cap_e), a per-entry scratch ent [cap_e, H] and a piece workspace of
+ * regnn_ns_gat_src_work_floats(cap_e, H * C) floats (piece_work_floats: what the caller has).
+ *   row pass     the atomic form's kernel with the atomics compiled out: ga, D, gs, gl, g_er /
+ *                g_xd and the slabs by the same instructions in the same order (the same bits as
+ *                the atomic form's); gl (GAT) / gs (GATv2) per entry into ent
+ *   source pass  per row u < n_out a walk over its slots in t_pos order, the sum in the lanes'
+ *                registers, written once by 16-byte stores:
+ *                  g_ft[u,h,:] = sum a[e,h] gy[v,h,:]       g_el[u,h] = sum gl[e,h]
+ *                  g_xs[u,h,d] = sum ( a[e,h] gy[v,h,d] + gs[e,h] att[h,d]
+ *                                      (xs[u,h,d] + xd[v,h,d] > 0 ? 1 : slope) )
+ *                EVERY row u < n_out is written (rows without slots, or u >= cap_src: exact zeros),
+ *                so the caller allocates without a fill. Segments of <= CHUNK slots: H C / 4 lanes
+ *                per source rounded up to a power of two (2 .. 64), 64 / lanes sources per wave,
+ *                rows wider than 64 vectors in several passes, the group's lanes fetching that
+ *                many slots' ids at once, eight slots' gathered rows in flight. Long
+ *                segments: a wave per piece into the workspace, then a wave per long row adding
+ *                its pieces in piece order.
+ * No float atomics anywhere: g_ft / g_el / g_xs are bitwise reproducible. The same (H, C) range,
+ * slab bounds and errors as the atomic forms; a missing index, ent or workspace pointer
+ * REGNN_EINVAL, a workspace below the query's value REGNN_EUNSUPPORTED; before any launch.
+ * Added without an ABI bump (the version stays 51): new symbols only. */
+#define REGNN_NS_TIDX_CHUNK 256
+int64_t regnn_ns_tidx_long_ints(int64_t cap_e);
+int64_t regnn_ns_tidx_work_ints(int64_t cap_src, int64_t cap_e);
+int regnn_ns_block_tidx(const int32_t* ptr, const int32_t* idx, int64_t cap_dst, int64_t n_src,
+                        int64_t cap_src, int64_t cap_e, int32_t* t_ptr, int32_t* t_pos,
+                        int32_t* t_row, int32_t* t_long, int64_t long_ints, int32_t* work,
+                        int64_t work_ints, hipStream_t stream);
+int64_t regnn_ns_gat_src_work_floats(int64_t cap_e, int32_t HC);
+int regnn_ns_gat_bwd_gather(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                            const float* el, const float* er, const float* tab, const float* ft,
+                            const float* a, const float* gy, float slope, int64_t cap_dst,
+                            int64_t n_src, int32_t H, int32_t C, int32_t n_rel, float* g_ft,
+                            float* g_el, float* g_er, float* slab, int32_t slab_rows,
+                            const int32_t* t_ptr, const int32_t* t_pos, const int32_t* t_row,
+                            const int32_t* t_long, int64_t cap_src, int64_t n_out, int64_t cap_e,
+                            float* ent, float* piece_work, int64_t piece_work_floats,
+                            hipStream_t stream);
+int regnn_ns_gatv2_bwd_gather(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                              const float* xs, const float* xd, const float* att,
+                              const float* tab, const float* a, const float* gy, float slope,
+                              int64_t cap_dst, int64_t n_src, int32_t H, int32_t C, int32_t n_rel,
+                              float* g_xs, float* g_xd, float* att_slab, float* tab_slab,
+                              int32_t slab_rows, const int32_t* t_ptr, const int32_t* t_pos,
+                              const int32_t* t_row, const int32_t* t_long, int64_t cap_src,
+                              int64_t n_out, int64_t cap_e, float* ent, float* piece_work,
+                              int64_t piece_work_floats, hipStream_t stream);
 
 /* Forward-only attention of the mag REGATConv / REGATv2Conv layers for the layer-wise
  * full-neighbour inference (mag/regnn_ns.py:348-369), in two calls.

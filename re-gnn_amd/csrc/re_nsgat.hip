@@ -11,7 +11,11 @@
 //                                   replayed graph needs no reset), den in entry order, a, out
 //   backward  ns_gat_bwd_kernel     ga, D, gs, gl per row; g_er and the relation slab in entry
 //                                   order; g_el / g_ft by float atomics (form (b), regnn_hip.h)
+//   or        ns_gat_bwd_rows_kernel  the same row pass without the atomics, gl per entry kept,
+//             + re_nsgat_src.h        then g_ft / g_el by a gather over the block's transposed
+//                                   index (form (a), regnn_ns_gat_bwd_gather): no atomics
 #include "re_nsgat_common.h"
+#include "re_nsgat_src.h"
 
 namespace regnn {
 namespace {
@@ -65,14 +69,19 @@ ns_gat_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
 // h in entry order, g_el and g_ft by atomics -- g_ft as one instruction per 64 consecutive
 // columns of a source row (256 contiguous bytes). A row of more than one chunk recomputes ga in
 // pass 2 (the same instructions on the same operands: the same bits).
-__global__ void __launch_bounds__(kBlock)
-ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
-                  const uint8_t* __restrict__ rel, const float* __restrict__ el,
-                  const float* __restrict__ er, const float* __restrict__ tab,
-                  const float* __restrict__ ft, const float* __restrict__ a,
-                  const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src, int H,
-                  int C, int n_rel, float* __restrict__ g_ft, float* __restrict__ g_el,
-                  float* __restrict__ g_er, float* __restrict__ slab) {
+//
+// kGather (regnn_ns_gat_bwd_gather's row pass): the same instructions in the same order with the
+// atomics compiled out -- gl[e,h] goes to the per-entry scratch `ent` (0 for an entry that takes
+// no part) and g_ft / g_el are left to the source pass (re_nsgat_src.h).
+template <bool kGather>
+__device__ __forceinline__ void
+ns_gat_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                const uint8_t* __restrict__ rel, const float* __restrict__ el,
+                const float* __restrict__ er, const float* __restrict__ tab,
+                const float* __restrict__ ft, const float* __restrict__ a,
+                const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src, int H,
+                int C, int n_rel, float* __restrict__ g_ft, float* __restrict__ g_el,
+                float* __restrict__ g_er, float* __restrict__ slab, float* __restrict__ ent) {
     extern __shared__ float bins_[];           // [kWaves][n_rel * H] when slab
     __shared__ float sa_[kWaves][kChunk * kMaxHeads];
     __shared__ float sg_[kWaves][kChunk * kMaxHeads];
@@ -151,8 +160,9 @@ ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
                 if (u >= 0) {
                     const float gs = sa[i] * (sg[i] - sD[hh]);
                     gl = pre_act(el, er, tab, u, v, sr[j], H, hh) > 0.f ? gs : gs * slope;
-                    unsafeAtomicAdd(g_el + int64_t(u) * H + hh, gl);
+                    if constexpr (!kGather) unsafeAtomicAdd(g_el + int64_t(u) * H + hh, gl);
                 }
+                if constexpr (kGather) ent[int64_t(cb + j) * H + hh] = gl;
                 sg[i] = gl;                    // (this lane's own slot)
             }
             wave_lds_sync();
@@ -164,12 +174,15 @@ ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
                     if (slab && r < n_rel) bins[r * H + lane] += gl;
                 }
             }
-            for (int col = lane; col < HC; col += 64) {
-                const int h = col / C;
-                const float g = gyr[col];
-                for (int j = 0; j < nc; ++j) {
-                    const int u = su[j];
-                    if (u >= 0) unsafeAtomicAdd(g_ft + int64_t(u) * HC + col, sa[j * H + h] * g);
+            if constexpr (!kGather) {
+                for (int col = lane; col < HC; col += 64) {
+                    const int h = col / C;
+                    const float g = gyr[col];
+                    for (int j = 0; j < nc; ++j) {
+                        const int u = su[j];
+                        if (u >= 0)
+                            unsafeAtomicAdd(g_ft + int64_t(u) * HC + col, sa[j * H + h] * g);
+                    }
                 }
             }
         }
@@ -183,6 +196,30 @@ ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
         for (int w = 1; w < kWaves; ++w) t += bins_[w * W + i];
         slab[int64_t(blockIdx.x) * W + i] = t;
     }
+}
+
+__global__ void __launch_bounds__(kBlock)
+ns_gat_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                  const uint8_t* __restrict__ rel, const float* __restrict__ el,
+                  const float* __restrict__ er, const float* __restrict__ tab,
+                  const float* __restrict__ ft, const float* __restrict__ a,
+                  const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src, int H,
+                  int C, int n_rel, float* __restrict__ g_ft, float* __restrict__ g_el,
+                  float* __restrict__ g_er, float* __restrict__ slab) {
+    ns_gat_bwd_body<false>(ptr, idx, rel, el, er, tab, ft, a, gy, slope, n_rows, n_src, H, C,
+                           n_rel, g_ft, g_el, g_er, slab, nullptr);
+}
+
+__global__ void __launch_bounds__(kBlock)
+ns_gat_bwd_rows_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                       const uint8_t* __restrict__ rel, const float* __restrict__ el,
+                       const float* __restrict__ er, const float* __restrict__ tab,
+                       const float* __restrict__ ft, const float* __restrict__ a,
+                       const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src,
+                       int H, int C, int n_rel, float* __restrict__ g_er,
+                       float* __restrict__ slab, float* __restrict__ ent) {
+    ns_gat_bwd_body<true>(ptr, idx, rel, el, er, tab, ft, a, gy, slope, n_rows, n_src, H, C,
+                          n_rel, nullptr, nullptr, g_er, slab, ent);
 }
 
 }  // namespace
@@ -233,4 +270,44 @@ extern "C" int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const ui
                        g_el, g_er, slab);
     REGNN_LAUNCH_CHECK();
     return REGNN_OK;
+}
+
+extern "C" int64_t regnn_ns_gat_src_work_floats(int64_t cap_e, int32_t HC) {
+    return cap_e < 0 || HC < 0 ? 0 : ns_src_work_floats(cap_e, HC);
+}
+
+extern "C" int regnn_ns_gat_bwd_gather(
+    const int32_t* ptr, const int32_t* idx, const uint8_t* rel, const float* el, const float* er,
+    const float* tab, const float* ft, const float* a, const float* gy, float slope,
+    int64_t cap_dst, int64_t n_src, int32_t H, int32_t C, int32_t n_rel, float* g_ft, float* g_el,
+    float* g_er, float* slab, int32_t slab_rows, const int32_t* t_ptr, const int32_t* t_pos,
+    const int32_t* t_row, const int32_t* t_long, int64_t cap_src, int64_t n_out, int64_t cap_e,
+    float* ent, float* piece_work, int64_t piece_work_floats, hipStream_t stream) {
+    if (!ptr || !idx || !el || !er || !ft || !a || !gy || !g_ft || !g_el || !g_er || !t_ptr ||
+        !t_pos || !t_row || !t_long || !ent || !piece_work || (tab && !rel) || (slab && !tab) ||
+        cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) || (slab && slab_rows < 1) ||
+        cap_src < 0 || n_out < 0 || cap_e < 0 || piece_work_floats < 0)
+        return REGNN_EINVAL;
+    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
+    if (slab && (int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS || slab_rows > REGNN_NS_GAT_WORK_FLOATS))
+        return REGNN_EUNSUPPORTED;
+    if (cap_e > 0x7ffffffe || cap_src > 0x7ffffffe || cap_dst > 0x7ffffffe ||
+        piece_work_floats < ns_src_work_floats(cap_e, int64_t(H) * C))
+        return REGNN_EUNSUPPORTED;
+    if (cap_dst > 0 || slab) {
+        // with a slab the launch has exactly slab_rows workgroups: each writes its row
+        const int grid = slab ? int(slab_rows) : ns_gat_grid(cap_dst);
+        const size_t lds = slab ? size_t(kWaves) * n_rel * H * sizeof(float) : 0;
+        hipLaunchKernelGGL(ns_gat_bwd_rows_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,
+                           rel, el, er, tab, ft, a, gy, slope, cap_dst, n_src, int(H), int(C),
+                           int(n_rel), g_er, slab, ent);
+        REGNN_LAUNCH_CHECK();
+    }
+    SrcArgs p{};
+    p.t_ptr = t_ptr, p.t_pos = t_pos, p.t_row = t_row, p.t_long = t_long;
+    p.a = a, p.ent = ent, p.gy = gy, p.slope = slope;
+    p.cap_src = cap_src, p.n_out = n_out, p.cap_dst = cap_dst, p.cap_e = int(cap_e);
+    p.max_pieces = int(ns_src_max_pieces(cap_e)), p.H = H, p.C = C;
+    p.g_main = g_ft, p.g_el = g_el, p.work = piece_work;
+    return ns_src_launch<false>(p, stream);
 }

@@ -13,7 +13,11 @@
 //                                    in entry order in registers, the relation bins by lane h, and
 //                                    ONE float atomic per element per entry into g_xs (message
 //                                    and score terms folded; form (b), regnn_hip.h)
+//   or        ns_gatv2_bwd_rows_kernel  the same row pass without the atomic, gs per entry kept,
+//             + re_nsgat_src.h       then g_xs by a gather over the block's transposed index
+//                                    (form (a), regnn_ns_gatv2_bwd_gather): no atomics
 #include "re_nsgat_common.h"
+#include "re_nsgat_src.h"
 
 namespace regnn {
 namespace {
@@ -77,15 +81,20 @@ ns_gatv2_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
 // of more than one chunk recomputes ga in pass 2 (the same instructions on the same operands: the
 // same bits) and carries its g_xd sums from chunk to chunk through the row it writes (the lane's
 // own stores: still one chain in entry order).
-template <int T>
-__global__ void __launch_bounds__(kBlock)
-ns_gatv2_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
-                    const uint8_t* __restrict__ rel, const float* __restrict__ xs,
-                    const float* __restrict__ xd, const float* __restrict__ att,
-                    const float* __restrict__ tab, const float* __restrict__ a,
-                    const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src,
-                    int H, int C, int n_rel, float* __restrict__ g_xs, float* __restrict__ g_xd,
-                    float* __restrict__ att_slab, float* __restrict__ tab_slab) {
+//
+// kGather (regnn_ns_gatv2_bwd_gather's row pass): the same instructions in the same order with the
+// atomic compiled out -- gs[e,h] goes to the per-entry scratch `ent` (0 for an entry that takes no
+// part) and g_xs is left to the source pass (re_nsgat_src.h).
+template <int T, bool kGather>
+__device__ __forceinline__ void
+ns_gatv2_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                  const uint8_t* __restrict__ rel, const float* __restrict__ xs,
+                  const float* __restrict__ xd, const float* __restrict__ att,
+                  const float* __restrict__ tab, const float* __restrict__ a,
+                  const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src,
+                  int H, int C, int n_rel, float* __restrict__ g_xs, float* __restrict__ g_xd,
+                  float* __restrict__ att_slab, float* __restrict__ tab_slab,
+                  float* __restrict__ ent) {
     extern __shared__ float dyn_[];            // [kWaves][n_rel * H] when tab_slab, then [H * C]
     __shared__ float sa_[kWaves][kChunk * kMaxHeads];
     __shared__ float sg_[kWaves][kChunk * kMaxHeads];
@@ -166,6 +175,7 @@ ns_gatv2_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
             for (int i = lane; i < nc * H; i += 64) {
                 const int hh = i % H;
                 sg[i] = sa[i] * (sg[i] - sD[hh]);      // gs (this lane's own slot; 0 where a is)
+                if constexpr (kGather) ent[int64_t(cb) * H + i] = sg[i];
             }
             wave_lds_sync();
             if (tab_slab && lane < H) {
@@ -185,13 +195,13 @@ ns_gatv2_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
                 for (int j = 0; j < nc; ++j) {
                     const int u = su[j];
                     if (u < 0) continue;
-                    float* dst = g_xs + int64_t(u) * HC + col;
+                    [[maybe_unused]] float* dst = g_xs + int64_t(u) * HC + col;
                     const float pre = xs[int64_t(u) * HC + col] + dv;
                     const float gs = sg[j * H + h];
                     const float q = gs * w * (pre > 0.f ? 1.f : slope);
                     gd += q;
                     ga = fmaf(gs, pre > 0.f ? pre : pre * slope, ga);
-                    unsafeAtomicAdd(dst, fmaf(sa[j * H + h], g, q));
+                    if constexpr (!kGather) unsafeAtomicAdd(dst, fmaf(sa[j * H + h], g, q));
                 }
                 gxdr[col] = gd;
                 gatt[t] = ga;
@@ -220,6 +230,33 @@ ns_gatv2_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
     }
     for (int i = threadIdx.x; i < HC; i += kBlock)
         att_slab[int64_t(blockIdx.x) * HC + i] = attred[i];
+}
+
+template <int T>
+__global__ void __launch_bounds__(kBlock)
+ns_gatv2_bwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                    const uint8_t* __restrict__ rel, const float* __restrict__ xs,
+                    const float* __restrict__ xd, const float* __restrict__ att,
+                    const float* __restrict__ tab, const float* __restrict__ a,
+                    const float* __restrict__ gy, float slope, int64_t n_rows, int64_t n_src,
+                    int H, int C, int n_rel, float* __restrict__ g_xs, float* __restrict__ g_xd,
+                    float* __restrict__ att_slab, float* __restrict__ tab_slab) {
+    ns_gatv2_bwd_body<T, false>(ptr, idx, rel, xs, xd, att, tab, a, gy, slope, n_rows, n_src, H,
+                                C, n_rel, g_xs, g_xd, att_slab, tab_slab, nullptr);
+}
+
+template <int T>
+__global__ void __launch_bounds__(kBlock)
+ns_gatv2_bwd_rows_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                         const uint8_t* __restrict__ rel, const float* __restrict__ xs,
+                         const float* __restrict__ xd, const float* __restrict__ att,
+                         const float* __restrict__ tab, const float* __restrict__ a,
+                         const float* __restrict__ gy, float slope, int64_t n_rows,
+                         int64_t n_src, int H, int C, int n_rel, float* __restrict__ g_xd,
+                         float* __restrict__ att_slab, float* __restrict__ tab_slab,
+                         float* __restrict__ ent) {
+    ns_gatv2_bwd_body<T, true>(ptr, idx, rel, xs, xd, att, tab, a, gy, slope, n_rows, n_src, H, C,
+                               n_rel, nullptr, g_xd, att_slab, tab_slab, ent);
 }
 
 inline int ns_gatv2_shape_rc(int32_t H, int32_t C) {
@@ -287,4 +324,53 @@ extern "C" int regnn_ns_gatv2_bwd(const int32_t* ptr, const int32_t* idx, const 
 #undef REGNN_NS_GATV2_BWD
     REGNN_LAUNCH_CHECK();
     return REGNN_OK;
+}
+
+extern "C" int regnn_ns_gatv2_bwd_gather(
+    const int32_t* ptr, const int32_t* idx, const uint8_t* rel, const float* xs, const float* xd,
+    const float* att, const float* tab, const float* a, const float* gy, float slope,
+    int64_t cap_dst, int64_t n_src, int32_t H, int32_t C, int32_t n_rel, float* g_xs, float* g_xd,
+    float* att_slab, float* tab_slab, int32_t slab_rows, const int32_t* t_ptr,
+    const int32_t* t_pos, const int32_t* t_row, const int32_t* t_long, int64_t cap_src,
+    int64_t n_out, int64_t cap_e, float* ent, float* piece_work, int64_t piece_work_floats,
+    hipStream_t stream) {
+    const bool slabs = att_slab || tab_slab;
+    if (!ptr || !idx || !xs || !xd || !att || !a || !gy || !g_xs || !g_xd || !t_ptr || !t_pos ||
+        !t_row || !t_long || !ent || !piece_work || (tab && !rel) || (tab_slab && !tab) ||
+        cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) || (slabs && slab_rows < 1) ||
+        cap_src < 0 || n_out < 0 || cap_e < 0 || piece_work_floats < 0)
+        return REGNN_EINVAL;
+    if (const int rc = ns_gatv2_shape_rc(H, C)) return rc;
+    if ((tab_slab && int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS) ||
+        (slabs && slab_rows > REGNN_NS_GAT_WORK_FLOATS))
+        return REGNN_EUNSUPPORTED;
+    const int HC = H * C;
+    if (cap_e > 0x7ffffffe || cap_src > 0x7ffffffe || cap_dst > 0x7ffffffe ||
+        piece_work_floats < ns_src_work_floats(cap_e, HC))
+        return REGNN_EUNSUPPORTED;
+    if (cap_dst > 0 || slabs) {
+        // with a slab the launch has exactly slab_rows workgroups: each writes its rows
+        const int grid = slabs ? int(slab_rows) : ns_gat_grid(cap_dst);
+        const size_t lds = ((tab_slab ? size_t(kWaves) * n_rel * H : 0) + (att_slab ? HC : 0)) *
+                           sizeof(float);
+#define REGNN_NS_GATV2_ROWS(T)                                                                   \
+    hipLaunchKernelGGL(ns_gatv2_bwd_rows_kernel<T>, dim3(grid), dim3(kBlock), lds, stream, ptr,  \
+                       idx, rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, int(H), int(C), \
+                       int(n_rel), g_xd, att_slab, tab_slab, ent)
+        if (HC <= 64) REGNN_NS_GATV2_ROWS(1);
+        else if (HC <= 128) REGNN_NS_GATV2_ROWS(2);
+        else if (HC <= 256) REGNN_NS_GATV2_ROWS(4);
+        else if (HC <= 512) REGNN_NS_GATV2_ROWS(8);
+        else if (HC <= 1024) REGNN_NS_GATV2_ROWS(16);
+        else REGNN_NS_GATV2_ROWS(32);
+#undef REGNN_NS_GATV2_ROWS
+        REGNN_LAUNCH_CHECK();
+    }
+    SrcArgs p{};
+    p.t_ptr = t_ptr, p.t_pos = t_pos, p.t_row = t_row, p.t_long = t_long;
+    p.a = a, p.ent = ent, p.gy = gy, p.xs = xs, p.xd = xd, p.att = att, p.slope = slope;
+    p.cap_src = cap_src, p.n_out = n_out, p.cap_dst = cap_dst, p.cap_e = int(cap_e);
+    p.max_pieces = int(ns_src_max_pieces(cap_e)), p.H = H, p.C = C;
+    p.g_main = g_xs, p.g_el = nullptr, p.work = piece_work;
+    return ns_src_launch<true>(p, stream);
 }

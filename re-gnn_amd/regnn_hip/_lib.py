@@ -122,6 +122,15 @@ _SIG = {
                            ctypes.c_int),
     "regnn_ns_gatv2_bwd": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P,
                             I32, P], ctypes.c_int),
+    "regnn_ns_tidx_long_ints": ([I64], I64),
+    "regnn_ns_tidx_work_ints": ([I64, I64], I64),
+    "regnn_ns_block_tidx": ([P, P, I64, I64, I64, I64, P, P, P, P, I64, P, I64, P], ctypes.c_int),
+    "regnn_ns_gat_src_work_floats": ([I64, I32], I64),
+    "regnn_ns_gat_bwd_gather": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P,
+                                 P, I32, P, P, P, P, I64, I64, I64, P, P, I64, P], ctypes.c_int),
+    "regnn_ns_gatv2_bwd_gather": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P,
+                                   P, P, I32, P, P, P, P, I64, I64, I64, P, P, I64, P],
+                                  ctypes.c_int),
     "regnn_mag_attn_fwd": ([P, P, P, P, I32, P, P, P, P, P, P, P, P, I64, I32, I32, F32, P, P],
                            ctypes.c_int),
     "regnn_mag_attn_epilogue": ([P, P, P, P, F32, P, P, P, P, F32, I32, I64, I32, I32, P, P],

@@ -139,6 +139,9 @@ class DeviceSampler:
         # sums_fresh[h]: the latest run_hops wrote hop h's layer-0 input sums (typed_sums path)
         self.sums_fresh = [False] * len(self.sizes_k)
         self.csc = [None] * len(self.sizes_k)      # per hop: (cnt, ptr, ent, long) or None
+        # per hop: the CSR block's canonical transposed index (ops.NsTidx; the gather form of the
+        # block attention backwards) or None; run_hops marks it stale, its build fresh
+        self.tidx = [None] * len(self.sizes_k)
         # per hop with an index: each slot's rank in its source's segment (regnn_ns_hop csc_rank)
         self.csc_rank = [None] * len(self.sizes_k)
         # csc_defer[h]: a strided hop h leaves its index's scan + placement to the fused step's
@@ -207,6 +210,9 @@ class DeviceSampler:
         hs = lambda h: strided if self.hop_strided[h] is None else self.hop_strided[h]  # noqa: E731
         rg = self.rg
         deferred, ride_place = -1, None
+        for t in self.tidx:
+            if t is not None:
+                t.fresh = False                # older than the batch these hops sample
         for h, k in enumerate(self.sizes_k):
             b, blk = self.hop_bufs[h], self.blocks[h]
             sh = hs(h)
@@ -1206,7 +1212,7 @@ class NSTrainer:
         # device_blocks: 'regat' too (mag.REGATConv reads the CSR blocks through ops.ns_gat), and
         # 'regatv2' with mag.GATV2_BLOCKS on (mag.REGATv2Conv through ops.ns_gatv2);
         # refused with a reason where the blocks do not apply (never a silent fall-back)
-        self._gat_blocks = False
+        self._gat_blocks = self._gat_src_gather = False
         if device_blocks and not self._blocks_ok:
             why_not = gat_blocks_unsupported(model, x_dict)
             if why_not is not None:
@@ -1215,6 +1221,10 @@ class NSTrainer:
                 raise ValueError("device_blocks=True: 'regat' runs on the module path, not the "
                                  "fused step")
             self._blocks_ok = self._gat_blocks = True
+            # ops.NS_GAT_SRC "gather": every slot owns its hops' transposed-index buffers and
+            # builds them beside the hops (_sample); the backwards then use no float atomics
+            from . import ops as _ops
+            self._gat_src_gather = _ops.ns_gat_src_mode() == "gather"
         self.params = [p for p in model.parameters() if p.requires_grad]
         # every parameter starts on a 16-byte boundary of the flat buckets (the fused step's
         # finalize sums and steps 4 aligned elements per thread); the pad elements stay zero.
@@ -1372,9 +1382,15 @@ class NSTrainer:
             blk.live_rows = s.sizes[h:h + 1]      # the block's live target rows (device count)
         if self._gat_blocks:
             # ops.ns_gat reads every hop in the CSR layout and differentiates by atomics
-            # (regnn_ns_gat_bwd form (b)): no strided hop, no transposed index, no input sums
+            # (regnn_ns_gat_bwd form (b)): no strided hop, no sampler index, no input sums; with
+            # ops.NS_GAT_SRC "gather" by a gather over each block's own index (form (a))
             for h, blk in enumerate(s.blocks):
                 blk.live_src = s.sizes[h + 1:h + 2]   # its live source rows (REGATConv's GEMMs)
+            if self._gat_src_gather:
+                from . import ops as _ops
+                for h, blk in enumerate(s.blocks):
+                    s.tidx[h] = blk.tidx = _ops.NsTidx(blk.n_dst, blk.n_src, blk.csr_idx.numel(),
+                                                       self.device)
             return
         if s.blocks[0].csr_idx.numel() <= 32768:
             _, cptr, cent, clong = s.csc[0] or s.enable_csc(0)
@@ -1484,6 +1500,12 @@ class NSTrainer:
             s.run_hops(before_sums=before_sums)
         else:                                 # the module path reads the CSR blocks
             s.run_hops(meta_only=self._module_lean, strided=False)
+            if self._gat_src_gather:
+                # each hop's transposed index right after the hops, on the stream that sampled
+                # them: prefetched with the batch, captured with the slot's sampling
+                from . import ops
+                for h, blk in enumerate(s.blocks):
+                    ops.ns_block_tidx(blk, out=s.tidx[h])
 
     def _pipelined_body(self, cur):
         """train slot `cur`'s batch while the batch of `ahead` steps later is sampled into slot
@@ -1623,6 +1645,9 @@ class NSTrainer:
         if not getattr(self, "_flat_zeroed", False):
             self.flat.zero_()
             self._flat_zeroed = True
+        if self._gat_src_gather and not all(t is not None and t.fresh for t in s.tidx):
+            raise RuntimeError("the blocks' transposed index is older than their batch (run_hops "
+                               "without the index build that follows it in _sample)")
         if self._blocks_ok:
             B = s.B
             # the sampler's int32 ids as they are (torch indexes with int32; the HIP ops convert

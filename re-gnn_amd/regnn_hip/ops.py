@@ -683,6 +683,87 @@ NS_GAT_WORK_FLOATS = 2048        # include/regnn_hip.h REGNN_NS_GAT_WORK_FLOATS
 NS_GAT_BWD_ROWS = {"n": int(os.environ.get("REGNN_NS_GAT_BWD_ROWS", "1024"))}
 
 
+# how regnn_ns_gat_bwd / regnn_ns_gatv2_bwd form the per-source sums (g_ft, g_el / g_xs):
+# "atomic": hardware float atomics into zero-filled buffers (run-dependent summation order);
+# "gather": a walk over the block's canonical transposed index (ns_block_tidx), no atomics, no
+# zero fill, the same bits on every run (regnn_ns_gat_bwd_gather / regnn_ns_gatv2_bwd_gather)
+NS_GAT_SRC = {"mode": os.environ.get("REGNN_NS_GAT_SRC", "atomic")}
+NS_TIDX_CHUNK = 256              # include/regnn_hip.h REGNN_NS_TIDX_CHUNK
+
+
+def ns_gat_src_mode():
+    """NS_GAT_SRC's mode, checked at first use"""
+    mode = NS_GAT_SRC["mode"]
+    if mode not in ("atomic", "gather"):
+        raise ValueError(f"REGNN_NS_GAT_SRC / ops.NS_GAT_SRC is {mode!r}: 'atomic' or 'gather'")
+    return mode
+
+
+class NsTidx:
+    """the buffers of a block's canonical transposed index (regnn_ns_block_tidx), capacity-sized:
+    t_ptr [cap_src + 1], t_pos / t_row [cap_e], t_long (the long segments' piece table) and the
+    build's scratch. fresh: the latest build read the block's current batch (the sampler clears
+    it when it resamples the block)."""
+
+    def __init__(self, cap_dst, cap_src, cap_e, device):
+        i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=device)  # noqa: E731
+        self.cap_dst, self.cap_src, self.cap_e = int(cap_dst), int(cap_src), int(cap_e)
+        self.t_ptr, self.t_pos, self.t_row = i32(cap_src + 1), i32(cap_e), i32(cap_e)
+        self.t_long = i32(L._so.regnn_ns_tidx_long_ints(self.cap_e))
+        self.work = i32(L._so.regnn_ns_tidx_work_ints(self.cap_src, self.cap_e))
+        self.n_src, self.fresh = 0, False
+
+    def fits(self, blk):
+        return (self.cap_dst == blk.n_dst and self.cap_src == blk.n_src and
+                self.cap_e == blk.csr_idx.numel() and self.t_ptr.device == blk.csr_idx.device)
+
+    def pieces(self):
+        """the piece table as a host list of (source, first slot, count, piece, pieces of the
+        row) (one host read: tests and tools)"""
+        t = self.t_long.cpu().tolist()
+        return [(t[4 + 4 * i], t[5 + 4 * i], t[6 + 4 * i], t[7 + 4 * i] >> 16,
+                 t[7 + 4 * i] & 0xffff) for i in range(t[0])]
+
+
+def ns_block_tidx(blk, out=None):
+    """the canonical transposed index of a device-sampled block in the CSR layout, on the current
+    stream, no host sync (capturable): per source its live entries' CSR positions ascending and
+    their rows (regnn_ns_block_tidx). out: an NsTidx to build into (None: a new one)."""
+    if getattr(blk, "strided_rows", None) is not None:
+        raise ValueError("ns_block_tidx reads the CSR layout; this block was sampled in the "
+                         "fixed-stride layout (strided_rows)")
+    if out is None:
+        out = NsTidx(blk.n_dst, blk.n_src, blk.csr_idx.numel(), blk.csr_idx.device)
+    elif not out.fits(blk):
+        raise ValueError("ns_block_tidx: the index buffers were sized for another block")
+    with timed("ns_block_tidx"):
+        L.call("regnn_ns_block_tidx", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx), out.cap_dst,
+               blk.n_src, out.cap_src, out.cap_e, L.ptr(out.t_ptr), L.ptr(out.t_pos),
+               L.ptr(out.t_row), L.ptr(out.t_long), out.t_long.numel(), L.ptr(out.work),
+               out.work.numel(), L.stream())
+    out.n_src, out.fresh = blk.n_src, True
+    return out
+
+
+_SRC_WORK = {}
+
+
+def _gat_src_args(blk, n_out, H, C, device):
+    """the gather form's extra arguments: the block's index (its own fresh one, else built here
+    on the current stream), the capacities, the per-entry scratch and the piece workspace"""
+    t = getattr(blk, "tidx", None)
+    if t is None or not t.fresh or not t.fits(blk):
+        t = ns_block_tidx(blk)
+    ent = torch.empty(t.cap_e, H, dtype=torch.float32, device=device)
+    n = int(L._so.regnn_ns_gat_src_work_floats(t.cap_e, H * C))
+    key = (n, device)
+    if key not in _SRC_WORK:
+        _SRC_WORK[key] = torch.empty(n, dtype=torch.float32, device=device)
+    work = _SRC_WORK[key]
+    return (L.ptr(t.t_ptr), L.ptr(t.t_pos), L.ptr(t.t_row), L.ptr(t.t_long), t.cap_src,
+            int(n_out), t.cap_e, L.ptr(ent), L.ptr(work), n), (t, ent, work)
+
+
 def ns_gat_bytes(E, n_dst, H, C, kind):
     """algorithmic HBM bytes of the sampled-block attention: per entry its id, relation, a and
     the gathered ft row (the backward: the row read for ga and the atomic row into g_ft), per
@@ -731,17 +812,31 @@ class _NsGat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _ga):
+        gather = ns_gat_src_mode() == "gather"
         el, er, t, ft, a = ctx.saved_tensors
         blk = ctx.blk
         H, C = int(ft.shape[1]), int(ft.shape[2])
         gy = gy.contiguous().float()
-        g_ft, g_el = torch.zeros_like(ft), torch.zeros_like(el)      # the atomics' targets
+        if gather:                             # every row written by the source pass
+            g_ft, g_el = torch.empty_like(ft), torch.empty_like(el)
+        else:
+            g_ft, g_el = torch.zeros_like(ft), torch.zeros_like(el)  # the atomics' targets
         g_er = torch.empty_like(er)
         n_rel = int(t.shape[0]) if t is not None else 0
         slab, rows = None, 0
         if t is not None and ctx.needs_input_grad[2]:
             rows = max(1, min(NS_GAT_BWD_ROWS["n"], NS_GAT_WORK_FLOATS, -(-blk.n_dst // 4)))
             slab = torch.empty(rows, n_rel * H, dtype=torch.float32, device=ft.device)
+        if gather:
+            extra, _keep = _gat_src_args(blk, ft.shape[0], H, C, ft.device)
+            with timed("ns_gat_bwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "bwd")):
+                L.call("regnn_ns_gat_bwd_gather", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+                       L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
+                       L.ptr(ft), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C,
+                       n_rel, L.ptr(g_ft), L.ptr(g_el), L.ptr(g_er), L.ptr(slab), rows, *extra,
+                       L.stream())
+            g_tab = _reduce(slab, n_rel * H).view(ctx.tab_shape) if slab is not None else None
+            return g_el, g_er, g_tab, g_ft, None, None
         with timed("ns_gat_bwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "bwd")):
             L.call("regnn_ns_gat_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
                    L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
@@ -759,7 +854,9 @@ def ns_gat(blk, el, er, tab, ft, slope=0.2, return_attn=False):
     (mag/regnn_layers.py:253-273). el / ft hold the block's source rows (>= blk.n_src rows; rows
     past the sampled ones unread, their gradients zero), er the blk.n_dst target rows; rows of
     out past the batch's live targets are zeros. The backward is gat_attention(global_max=True)'s
-    (the maximum a constant); its per-source sums use float atomics (regnn_ns_gat_bwd).
+    (the maximum a constant); its per-source sums use float atomics (regnn_ns_gat_bwd), or with
+    NS_GAT_SRC "gather" a walk over the block's transposed index (regnn_ns_gat_bwd_gather: no
+    atomics, the same bits on every run).
     return_attn: also a [blk capacity entries, H] (no gradient)."""
     out, a = _NsGat.apply(el, er, tab, ft, blk, slope)
     return (out, a) if return_attn else out
@@ -821,11 +918,13 @@ class _NsGatv2(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _ga):
+        gather = ns_gat_src_mode() == "gather"
         xs, xd, w, t, a = ctx.saved_tensors
         blk = ctx.blk
         H, C = int(xs.shape[1]), int(xs.shape[2])
         gy = gy.contiguous().float()
-        g_xs = torch.zeros_like(xs)                                  # the atomics' target
+        # (gather: every row written by the source pass; else the atomics' target)
+        g_xs = torch.empty_like(xs) if gather else torch.zeros_like(xs)
         g_xd = torch.empty_like(xd)
         n_rel = int(t.shape[0]) if t is not None else 0
         need_att = ctx.needs_input_grad[2]
@@ -838,6 +937,17 @@ class _NsGatv2(torch.autograd.Function):
                 att_slab = torch.empty(rows, H * C, dtype=torch.float32, device=xs.device)
             if need_tab:
                 tab_slab = torch.empty(rows, n_rel * H, dtype=torch.float32, device=xs.device)
+        if gather:
+            extra, _keep = _gat_src_args(blk, xs.shape[0], H, C, xs.device)
+            with timed("ns_gatv2_bwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "bwd")):
+                L.call("regnn_ns_gatv2_bwd_gather", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+                       L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
+                       L.ptr(t), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C,
+                       n_rel, L.ptr(g_xs), L.ptr(g_xd), L.ptr(att_slab), L.ptr(tab_slab), rows,
+                       *extra, L.stream())
+            g_att = _reduce(att_slab, H * C).view(ctx.att_shape) if need_att else None
+            g_tab = _reduce(tab_slab, n_rel * H).view(ctx.tab_shape) if need_tab else None
+            return g_xs, g_xd, g_att, g_tab, None, None
         with timed("ns_gatv2_bwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "bwd")):
             L.call("regnn_ns_gatv2_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
                    L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
@@ -859,7 +969,8 @@ def ns_gatv2(blk, xs, xd, att, tab, slope=0.2, return_attn=False):
     [n_rel, H] or None; rows of out past the batch's live targets are zeros. H in 1..16, C a
     multiple of 4 in [4, 512], H * C <= 2048. The backward is the global-max softmax's with the
     maximum a constant; g_xd, g_att and g_tab are summed in a fixed order, g_xs by float atomics
-    (regnn_ns_gatv2_bwd). return_attn: also a [blk capacity entries, H] (no gradient)."""
+    (regnn_ns_gatv2_bwd) or, with NS_GAT_SRC "gather", by a walk over the block's transposed index
+    (regnn_ns_gatv2_bwd_gather: the same bits on every run). return_attn: also a [blk capacity entries, H] (no gradient)."""
     out, a = _NsGatv2.apply(xs, xd, att, tab, blk, slope)
     return (out, a) if return_attn else out
 

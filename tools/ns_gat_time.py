@@ -2,7 +2,7 @@
 default exact-size path, in one process (bench.py times the 'regcn' step only):
 
     python tools/ns_gat_time.py [--model regat] [--scale 1] [--batch 512] [--steps 20]
-                                [--rounds 7] [--kernel-steps 0] [--out FILE]
+                                [--rounds 7] [--kernel-steps 0] [--src atomic] [--out FILE]
 
 One graph -- mag_like(scale), 128-d inputs, REGNN 'regat' hidden 64 x 8 heads, 349 classes,
 fan-out [25, 20], dropout 0.5, FlatAdam -- and two trainers over it:
@@ -18,6 +18,13 @@ fan-out [25, 20], dropout 0.5, FlatAdam -- and two trainers over it:
 through ops.ns_gatv2), A is the gatv2_scores / amax / edge_softmax / head SpMM chain.
 --kernel-steps K > 0: after the windows, K more eager steps of B under ops' event timers; the
 attention operator's device time per step (both layers) goes into "kernel_us_per_step".
+
+--src gather: a third trainer C, path B with ops.NS_GAT_SRC = "gather" (the backwards' per-source
+sums by a gather over each block's transposed index, built on the sampler's stream: no float
+atomics), captured as B is; the windows then alternate A, B, C, so gather is timed against the
+atomic form in the same process. Its peak memory is measured as B's is, and --kernel-steps times
+both forms ("kernel_us_per_step" for B, "kernel_us_per_step_gather" for C, the latter with the
+index build, ns_block_tidx, on the sampler's stream).
 
 After warm-up runs of both, `rounds` timed windows of `steps` steps each, alternating A and B; a
 window is a host clock around the steps ending in a device synchronise. Prints (and with --out
@@ -52,11 +59,12 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--model", choices=["regat", "regatv2"], default="regat")
     ap.add_argument("--kernel-steps", type=int, default=0)
+    ap.add_argument("--src", choices=["atomic", "gather"], default="atomic")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("ns_gat_time: needs the GPU (no CPU timing)")
-    from regnn_hip import mag, synth
+    from regnn_hip import mag, ops, synth
     from regnn_hip.graph import RelGraph
     from regnn_hip.ns import NSTrainer
     dev = "cuda"
@@ -105,6 +113,21 @@ def main():
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated()
     runs = {"exact_eager": lambda k: run_a(tr_a, k), "device_blocks_captured": tr_b.run_steps}
+    trainers = {"exact_eager": tr_a, "device_blocks_captured": tr_b}
+    peak_c = base_c = None
+    if args.src == "gather":
+        base_c = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        ops.NS_GAT_SRC["mode"] = "gather"      # read when C is built and when it is captured
+        tr_c = trainer(device_blocks=True)
+        assert tr_c._gat_src_gather and tr_c.pipelined and tr_c.ahead == 1
+        tr_c.capture(warmup=2)
+        tr_c.run_steps(args.warmup)
+        torch.cuda.synchronize()
+        peak_c = torch.cuda.max_memory_allocated()
+        ops.NS_GAT_SRC["mode"] = "atomic"
+        runs["device_blocks_gather_captured"] = tr_c.run_steps
+        trainers["device_blocks_gather_captured"] = tr_c
     us = {k: [] for k in runs}
     for _ in range(args.rounds):
         for k, run in runs.items():
@@ -121,17 +144,27 @@ def main():
     for k, v in us.items():
         out[k] = {"us_per_step_median": round(statistics.median(v), 1),
                   "min": round(min(v), 1), "max": round(max(v), 1),
-                  "final_loss": float((tr_a if k == "exact_eager" else tr_b).loss)}
+                  "final_loss": float(trainers[k].loss)}
+    if peak_c is not None:
+        out["device_blocks_gather_peak_bytes"] = int(peak_c)
+        out["allocated_before_device_blocks_gather_bytes"] = int(base_c)
     if args.kernel_steps > 0:
         from regnn_hip import profile
-        profile.enable()
-        for _ in range(args.kernel_steps):
-            tr_b.step()
-        torch.cuda.synchronize()
-        out["kernel_us_per_step"] = {
-            k: round(v[2] * 1e3 / args.kernel_steps, 1)
-            for k, v in sorted(profile.summary().items()) if k.startswith("ns_gat")}
-        profile.enable(False)
+        forms = [("kernel_us_per_step", tr_b, "atomic")]
+        if args.src == "gather":
+            forms.append(("kernel_us_per_step_gather", tr_c, "gather"))
+        for key, tr, mode in forms:
+            ops.NS_GAT_SRC["mode"] = mode      # eager steps read it at every backward
+            profile.enable()
+            for _ in range(args.kernel_steps):
+                tr.step()
+            torch.cuda.synchronize()
+            out[key] = {
+                k: round(v[2] * 1e3 / args.kernel_steps, 1)
+                for k, v in sorted(profile.summary().items())
+                if k.startswith("ns_gat") or k == "ns_block_tidx"}
+            profile.enable(False)
+        ops.NS_GAT_SRC["mode"] = "atomic"
     line = json.dumps(out)
     print(line)
     if args.out:
