@@ -952,9 +952,10 @@ int regnn_ns_gatv2_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* re
  * tiles of 1024 sources in three launches (the tiles' sums, ONE workgroup scanning those, each
  * tile again with its offset: t_ptr, the cursors back to zero, the pieces); placement by an atomic
  * cursor into the scratch; then a thread per slot ranking its position among its segment's (a
- * count: order-free) and writing the entry at that rank. REGNN_NS_TIDX_CHUNK = 256: a piece is walked by one wave in slot order, and
- * 256 slots of an 8 x 64 row are 512 KB of gathered gy rows per wave -- long enough to amortise
- * the piece's partial row, short enough that a 500-entry hub spreads over several waves.
+ * count: order-free) and writing the entry at that rank. REGNN_NS_TIDX_CHUNK = 256: a piece is
+ * walked by one wave in slot order, and 256 slots of an 8 x 64 row are 512 KB of gathered gy rows
+ * per wave -- long enough to amortise the piece's partial row, short enough that a 500-entry hub
+ * spreads over several waves.
  * A NULL pointer, a negative size or n_src > cap_src: REGNN_EINVAL. A capacity above 2^31 - 2,
  * cap_e / CHUNK + 1 > 65535 (the piece word's 16-bit fields), or long_ints / work_ints below the
  * query functions' values: REGNN_EUNSUPPORTED. Both before any launch.

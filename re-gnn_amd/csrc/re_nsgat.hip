@@ -63,16 +63,17 @@ ns_gat_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
     ns_softmax_aggregate(ptr, idx, ft, wgmax, n_wg, n_rows, n_src, H, C, a, out);
 }
 
-// One wave per row. Pass 1 over the row's chunks: ga[e,h] = <gy[v,h,:], ft[u,h,:]> (a lane per
-// (entry, head), columns in order) and D[v,h] = sum a ga in entry order. Pass 2: gs, gl (the
-// pre-activation's sign recomputed from el + er + tab), g_er and the wave's relation bins by lane
-// h in entry order, g_el and g_ft by atomics -- g_ft as one instruction per 64 consecutive
-// columns of a source row (256 contiguous bytes). A row of more than one chunk recomputes ga in
-// pass 2 (the same instructions on the same operands: the same bits).
+// One wave per row. Pass 1 over the row's chunks (NsRow, re_nsgat_common.h, shared with GATv2):
+// ga[e,h] = <gy[v,h,:], ft[u,h,:]> (a lane per (entry, head), columns in order) and D[v,h] =
+// sum a ga in entry order. Pass 2, this operator's own: gs, gl (the pre-activation's sign
+// recomputed from el + er + tab), g_er and the wave's relation bins by lane h in entry order, g_el
+// and g_ft by atomics -- g_ft as one instruction per 64 consecutive columns of a source row (256
+// contiguous bytes). A row of more than one chunk recomputes ga in pass 2 (the same instructions
+// on the same operands: the same bits).
 //
-// kGather (regnn_ns_gat_bwd_gather's row pass): the same instructions in the same order with the
-// atomics compiled out -- gl[e,h] goes to the per-entry scratch `ent` (0 for an entry that takes
-// no part) and g_ft / g_el are left to the source pass (re_nsgat_src.h).
+// kGather (regnn_ns_gat_bwd_gather's row pass): this one body with the atomics compiled out --
+// gl[e,h] goes to the per-entry scratch `ent` (0 for an entry that takes no part) and g_ft / g_el
+// are left to the source pass (re_nsgat_src.h).
 template <bool kGather>
 __device__ __forceinline__ void
 ns_gat_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
@@ -83,23 +84,11 @@ ns_gat_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx
                 int C, int n_rel, float* __restrict__ g_ft, float* __restrict__ g_el,
                 float* __restrict__ g_er, float* __restrict__ slab, float* __restrict__ ent) {
     extern __shared__ float bins_[];           // [kWaves][n_rel * H] when slab
-    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
-    __shared__ float sg_[kWaves][kChunk * kMaxHeads];
-    __shared__ int su_[kWaves][kChunk];
-    __shared__ int sr_[kWaves][kChunk];
-    __shared__ float sD_[kWaves][kMaxHeads];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* sa = sa_[wave];
-    float* sg = sg_[wave];
-    int* su = su_[wave];
-    int* sr = sr_[wave];
-    float* sD = sD_[wave];
+    const NsRow s = ns_row(idx, rel, tab != nullptr, ft, a, n_src, H, C);
     const int W = n_rel * H;
     float* bins = bins_ + wave * W;
-    if (slab) {
-        for (int i = threadIdx.x; i < kWaves * W; i += kBlock) bins_[i] = 0.f;
-        __syncthreads();
-    }
+    if (slab) ns_bins_zero(bins_, W);
     const int HC = H * C;
     for (int64_t v = int64_t(blockIdx.x) * kWaves + wave; v < n_rows;
          v += int64_t(gridDim.x) * kWaves) {
@@ -109,68 +98,30 @@ ns_gat_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx
             continue;
         }
         const float* gyr = gy + v * HC;
-        // the chunk [cb, cb + nc): ids, a and ga into LDS
-        auto fill = [&](int cb, int nc) {
-            wave_lds_sync();
-            for (int j = lane; j < nc; j += 64) {
-                const int u = idx[cb + j];
-                su[j] = src_ok(u, n_src) ? u : -1;
-                sr[j] = tab ? int(rel[cb + j]) : 0;
-            }
-            for (int i = lane; i < nc * H; i += 64) {
-                const int j = i / H, hh = i - j * H;
-                const int u = idx[cb + j];
-                float d = 0.f, w = 0.f;
-                if (src_ok(u, n_src)) {
-                    w = a[int64_t(cb + j) * H + hh];
-                    const float4* gp = reinterpret_cast<const float4*>(gyr + hh * C);
-                    const float4* xp = reinterpret_cast<const float4*>(
-                        ft + int64_t(u) * HC + hh * C);
-                    for (int c = 0; c < (C >> 2); ++c) {
-                        const float4 g = gp[c], x = xp[c];
-                        d = fmaf(g.x, x.x, d);
-                        d = fmaf(g.y, x.y, d);
-                        d = fmaf(g.z, x.z, d);
-                        d = fmaf(g.w, x.w, d);
-                    }
-                }
-                sa[i] = w;
-                sg[i] = d;
-            }
-            wave_lds_sync();
-        };
-        const bool one = e1 - e0 <= kChunk;
-        float D = 0.f;
-        for (int cb = e0; cb < e1; cb += kChunk) {
-            const int nc = min(kChunk, e1 - cb);
-            fill(cb, nc);
-            if (lane < H)
-                for (int j = 0; j < nc; ++j) D = fmaf(sa[j * H + lane], sg[j * H + lane], D);
-        }
-        if (lane < H) sD[lane] = D;
+        const bool one = s.pass1(gyr, e0, e1);
         float ger = 0.f;
         for (int cb = e0; cb < e1; cb += kChunk) {
             const int nc = min(kChunk, e1 - cb);
-            if (!one) fill(cb, nc);
+            if (!one) s.fill(gyr, cb, nc);
             else wave_lds_sync();              // sD written
             for (int i = lane; i < nc * H; i += 64) {
                 const int j = i / H, hh = i - j * H;
-                const int u = su[j];
+                const int u = s.su[j];
                 float gl = 0.f;
                 if (u >= 0) {
-                    const float gs = sa[i] * (sg[i] - sD[hh]);
-                    gl = pre_act(el, er, tab, u, v, sr[j], H, hh) > 0.f ? gs : gs * slope;
+                    const float gs = s.sa[i] * (s.sg[i] - s.sD[hh]);
+                    gl = pre_act(el, er, tab, u, v, s.sr[j], H, hh) > 0.f ? gs : gs * slope;
                     if constexpr (!kGather) unsafeAtomicAdd(g_el + int64_t(u) * H + hh, gl);
                 }
                 if constexpr (kGather) ent[int64_t(cb + j) * H + hh] = gl;
-                sg[i] = gl;                    // (this lane's own slot)
+                s.sg[i] = gl;                  // (this lane's own slot)
             }
             wave_lds_sync();
             if (lane < H) {
                 for (int j = 0; j < nc; ++j) {
-                    const float gl = sg[j * H + lane];
+                    const float gl = s.sg[j * H + lane];
                     ger += gl;
-                    const int r = sr[j];
+                    const int r = s.sr[j];
                     if (slab && r < n_rel) bins[r * H + lane] += gl;
                 }
             }
@@ -179,23 +130,16 @@ ns_gat_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx
                     const int h = col / C;
                     const float g = gyr[col];
                     for (int j = 0; j < nc; ++j) {
-                        const int u = su[j];
+                        const int u = s.su[j];
                         if (u >= 0)
-                            unsafeAtomicAdd(g_ft + int64_t(u) * HC + col, sa[j * H + h] * g);
+                            unsafeAtomicAdd(g_ft + int64_t(u) * HC + col, s.sa[j * H + h] * g);
                     }
                 }
             }
         }
         if (lane < H) g_er[v * H + lane] = ger;
     }
-    if (!slab) return;
-    __syncthreads();
-    for (int i = threadIdx.x; i < W; i += kBlock) {
-        float t = bins_[i];                    // the waves' bins in wave order
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) t += bins_[w * W + i];
-        slab[int64_t(blockIdx.x) * W + i] = t;
-    }
+    if (slab) ns_bins_store(bins_, W, slab);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -220,6 +164,45 @@ ns_gat_bwd_rows_kernel(const int32_t* __restrict__ ptr, const int32_t* __restric
                        float* __restrict__ slab, float* __restrict__ ent) {
     ns_gat_bwd_body<true>(ptr, idx, rel, el, er, tab, ft, a, gy, slope, n_rows, n_src, H, C,
                           n_rel, nullptr, nullptr, g_er, slab, ent);
+}
+
+// Both backward entry points (x: the gather form's own arguments). The refusals, before any
+// launch: invalid arguments, the shape gate, the budgets, then the gather form's capacities. The
+// row pass: with a slab exactly slab_rows workgroups (each writes its row), without one and
+// without rows nothing. The source pass runs either way: every g_ft / g_el row is written.
+template <bool kGather>
+inline int gat_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel, const float* el,
+                   const float* er, const float* tab, const float* ft, const float* a,
+                   const float* gy, float slope, int64_t cap_dst, int64_t n_src, int32_t H,
+                   int32_t C, int32_t n_rel, float* g_ft, float* g_el, float* g_er, float* slab,
+                   int32_t slab_rows, const SrcIdx& x, hipStream_t stream) {
+    if (!ptr || !idx || !el || !er || !ft || !a || !gy || !g_ft || !g_el || !g_er ||
+        (tab && !rel) || (slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 ||
+        (tab && n_rel < 1) || (slab && slab_rows < 1) || (kGather && x.invalid()))
+        return REGNN_EINVAL;
+    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
+    if (slab &&
+        (int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS || slab_rows > REGNN_NS_GAT_WORK_FLOATS))
+        return REGNN_EUNSUPPORTED;
+    if (kGather && x.over(cap_dst, int64_t(H) * C)) return REGNN_EUNSUPPORTED;
+    if (cap_dst > 0 || slab) {
+        const int grid = slab ? int(slab_rows) : ns_gat_grid(cap_dst);
+        const size_t lds = slab ? size_t(kWaves) * n_rel * H * sizeof(float) : 0;
+        if constexpr (kGather) {
+            hipLaunchKernelGGL(ns_gat_bwd_rows_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr,
+                               idx, rel, el, er, tab, ft, a, gy, slope, cap_dst, n_src, int(H),
+                               int(C), int(n_rel), g_er, slab, x.ent);
+        } else {
+            hipLaunchKernelGGL(ns_gat_bwd_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,
+                               rel, el, er, tab, ft, a, gy, slope, cap_dst, n_src, int(H), int(C),
+                               int(n_rel), g_ft, g_el, g_er, slab);
+        }
+        REGNN_LAUNCH_CHECK();
+    }
+    if constexpr (kGather)
+        return ns_src_launch<false>(ns_src_args(x, a, gy, slope, cap_dst, H, C, g_ft, g_el),
+                                    stream);
+    return REGNN_OK;
 }
 
 }  // namespace
@@ -254,22 +237,8 @@ extern "C" int regnn_ns_gat_bwd(const int32_t* ptr, const int32_t* idx, const ui
                                 int64_t cap_dst, int64_t n_src, int32_t H, int32_t C,
                                 int32_t n_rel, float* g_ft, float* g_el, float* g_er, float* slab,
                                 int32_t slab_rows, hipStream_t stream) {
-    if (!ptr || !idx || !el || !er || !ft || !a || !gy || !g_ft || !g_el || !g_er ||
-        (tab && !rel) || (slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 ||
-        (tab && n_rel < 1) || (slab && slab_rows < 1))
-        return REGNN_EINVAL;
-    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
-    if (slab && (int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS || slab_rows > REGNN_NS_GAT_WORK_FLOATS))
-        return REGNN_EUNSUPPORTED;
-    if (cap_dst == 0 && !slab) return REGNN_OK;
-    // with a slab the launch has exactly slab_rows workgroups: each writes its row
-    const int grid = slab ? int(slab_rows) : ns_gat_grid(cap_dst);
-    const size_t lds = slab ? size_t(kWaves) * n_rel * H * sizeof(float) : 0;
-    hipLaunchKernelGGL(ns_gat_bwd_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx, rel, el,
-                       er, tab, ft, a, gy, slope, cap_dst, n_src, int(H), int(C), int(n_rel), g_ft,
-                       g_el, g_er, slab);
-    REGNN_LAUNCH_CHECK();
-    return REGNN_OK;
+    return gat_bwd<false>(ptr, idx, rel, el, er, tab, ft, a, gy, slope, cap_dst, n_src, H, C,
+                          n_rel, g_ft, g_el, g_er, slab, slab_rows, SrcIdx{}, stream);
 }
 
 extern "C" int64_t regnn_ns_gat_src_work_floats(int64_t cap_e, int32_t HC) {
@@ -283,31 +252,8 @@ extern "C" int regnn_ns_gat_bwd_gather(
     float* g_er, float* slab, int32_t slab_rows, const int32_t* t_ptr, const int32_t* t_pos,
     const int32_t* t_row, const int32_t* t_long, int64_t cap_src, int64_t n_out, int64_t cap_e,
     float* ent, float* piece_work, int64_t piece_work_floats, hipStream_t stream) {
-    if (!ptr || !idx || !el || !er || !ft || !a || !gy || !g_ft || !g_el || !g_er || !t_ptr ||
-        !t_pos || !t_row || !t_long || !ent || !piece_work || (tab && !rel) || (slab && !tab) ||
-        cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) || (slab && slab_rows < 1) ||
-        cap_src < 0 || n_out < 0 || cap_e < 0 || piece_work_floats < 0)
-        return REGNN_EINVAL;
-    if (const int rc = ns_gat_shape_rc(H, C)) return rc;
-    if (slab && (int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS || slab_rows > REGNN_NS_GAT_WORK_FLOATS))
-        return REGNN_EUNSUPPORTED;
-    if (cap_e > 0x7ffffffe || cap_src > 0x7ffffffe || cap_dst > 0x7ffffffe ||
-        piece_work_floats < ns_src_work_floats(cap_e, int64_t(H) * C))
-        return REGNN_EUNSUPPORTED;
-    if (cap_dst > 0 || slab) {
-        // with a slab the launch has exactly slab_rows workgroups: each writes its row
-        const int grid = slab ? int(slab_rows) : ns_gat_grid(cap_dst);
-        const size_t lds = slab ? size_t(kWaves) * n_rel * H * sizeof(float) : 0;
-        hipLaunchKernelGGL(ns_gat_bwd_rows_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,
-                           rel, el, er, tab, ft, a, gy, slope, cap_dst, n_src, int(H), int(C),
-                           int(n_rel), g_er, slab, ent);
-        REGNN_LAUNCH_CHECK();
-    }
-    SrcArgs p{};
-    p.t_ptr = t_ptr, p.t_pos = t_pos, p.t_row = t_row, p.t_long = t_long;
-    p.a = a, p.ent = ent, p.gy = gy, p.slope = slope;
-    p.cap_src = cap_src, p.n_out = n_out, p.cap_dst = cap_dst, p.cap_e = int(cap_e);
-    p.max_pieces = int(ns_src_max_pieces(cap_e)), p.H = H, p.C = C;
-    p.g_main = g_ft, p.g_el = g_el, p.work = piece_work;
-    return ns_src_launch<false>(p, stream);
+    const SrcIdx x{t_ptr, t_pos, t_row, t_long, cap_src, n_out, cap_e, ent, piece_work,
+                   piece_work_floats};
+    return gat_bwd<true>(ptr, idx, rel, el, er, tab, ft, a, gy, slope, cap_dst, n_src, H, C, n_rel,
+                         g_ft, g_el, g_er, slab, slab_rows, x, stream);
 }

@@ -1,7 +1,8 @@
 // What the two sampled-block attention operators share (re_nsgat.hip: REGATConv's scores,
-// re_nsgatv2.hip: REGATv2Conv's): the wave helpers, the shape gate, the grid, and the second
-// forward launch -- the global-max softmax and the aggregation over a block whose scores already
-// lie in the `a` buffer with one maximum per workgroup in `wgmax`.
+// re_nsgatv2.hip: REGATv2Conv's): the wave helpers, the shape gate, the grid, the second forward
+// launch -- the global-max softmax and the aggregation over a block whose scores already lie in
+// the `a` buffer with one maximum per workgroup in `wgmax` -- and the opening of both backwards'
+// row pass (NsRow: the chunk fill and pass 1; the relation bins' zeroing and wave-order sum).
 #pragma once
 #include "regnn_common.h"
 
@@ -126,6 +127,99 @@ __device__ __forceinline__ void ns_softmax_aggregate(
             }
             if (active) *reinterpret_cast<float4*>(orow + 4 * c4) = acc;
         }
+    }
+}
+
+// What the two backwards' row passes share (ns_gat_bwd_body, ns_gatv2_bwd_body): a wave's view of
+// one row, 64 entries at a time. xt is the message table (ft / xs), with_rel whether rel is read.
+// In LDS: sa [kChunk * H] a; sg [kChunk * H] ga, which pass 2 overwrites with gl / gs; su [kChunk]
+// the source id, -1 for an entry that takes no part; sr [kChunk] the relation; sD [H].
+struct NsRow {
+    const int32_t* idx;
+    const uint8_t* rel;
+    const float *xt, *a;
+    int64_t n_src;
+    int H, C;
+    bool with_rel;
+    float *sa, *sg;
+    int *su, *sr;
+    float* sD;
+
+    // the chunk [cb, cb + nc) of the row whose gy is gyr: ids, a and ga into LDS
+    __device__ __forceinline__ void fill(const float* gyr, int cb, int nc) const {
+        const int lane = threadIdx.x & 63, HC = H * C;
+        wave_lds_sync();
+        for (int j = lane; j < nc; j += 64) {
+            const int u = idx[cb + j];
+            su[j] = src_ok(u, n_src) ? u : -1;
+            sr[j] = with_rel ? int(rel[cb + j]) : 0;
+        }
+        for (int i = lane; i < nc * H; i += 64) {
+            const int j = i / H, hh = i - j * H;
+            const int u = idx[cb + j];
+            float d = 0.f, w = 0.f;
+            if (src_ok(u, n_src)) {
+                w = a[int64_t(cb + j) * H + hh];
+                const float4* gp = reinterpret_cast<const float4*>(gyr + hh * C);
+                const float4* xp = reinterpret_cast<const float4*>(xt + int64_t(u) * HC + hh * C);
+                for (int c = 0; c < (C >> 2); ++c) {
+                    const float4 g = gp[c], x = xp[c];
+                    d = fmaf(g.x, x.x, d);
+                    d = fmaf(g.y, x.y, d);
+                    d = fmaf(g.z, x.z, d);
+                    d = fmaf(g.w, x.w, d);
+                }
+            }
+            sa[i] = w;
+            sg[i] = d;
+        }
+        wave_lds_sync();
+    }
+
+    // pass 1 over the row [e0, e1): D[h] = sum a ga in entry order into sD. Returns `one`: the
+    // row is a single chunk, which pass 2 then finds in LDS.
+    __device__ __forceinline__ bool pass1(const float* gyr, int e0, int e1) const {
+        const int lane = threadIdx.x & 63;
+        const bool one = e1 - e0 <= kChunk;
+        float D = 0.f;
+        for (int cb = e0; cb < e1; cb += kChunk) {
+            const int nc = min(kChunk, e1 - cb);
+            fill(gyr, cb, nc);
+            if (lane < H)
+                for (int j = 0; j < nc; ++j) D = fmaf(sa[j * H + lane], sg[j * H + lane], D);
+        }
+        if (lane < H) sD[lane] = D;
+        return one;
+    }
+};
+
+__device__ __forceinline__ NsRow ns_row(const int32_t* idx, const uint8_t* rel, bool with_rel,
+                                        const float* xt, const float* a, int64_t n_src, int H,
+                                        int C) {
+    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
+    __shared__ float sg_[kWaves][kChunk * kMaxHeads];
+    __shared__ int su_[kWaves][kChunk];
+    __shared__ int sr_[kWaves][kChunk];
+    __shared__ float sD_[kWaves][kMaxHeads];
+    const int wave = threadIdx.x >> 6;
+    return {idx, rel, xt, a, n_src, H, C, with_rel, sa_[wave], sg_[wave], su_[wave], sr_[wave],
+            sD_[wave]};
+}
+
+// the workgroup's per-wave relation bins [kWaves][W] (dynamic LDS): zeroed before the rows ...
+__device__ __forceinline__ void ns_bins_zero(float* bins_, int W) {
+    for (int i = threadIdx.x; i < kWaves * W; i += kBlock) bins_[i] = 0.f;
+    __syncthreads();
+}
+
+// ... and added in wave order into the workgroup's slab row after them
+__device__ __forceinline__ void ns_bins_store(const float* bins_, int W, float* slab) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < W; i += kBlock) {
+        float t = bins_[i];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) t += bins_[w * W + i];
+        slab[int64_t(blockIdx.x) * W + i] = t;
     }
 }
 

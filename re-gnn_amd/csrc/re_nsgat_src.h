@@ -234,6 +234,37 @@ inline int64_t ns_src_work_floats(int64_t cap_e, int64_t HC) {
     return ns_src_max_pieces(cap_e) * (HC + kSrcPad);
 }
 
+// The gather forms' own arguments, in the entry points' order (regnn_hip.h). invalid(): a NULL or
+// negative one, REGNN_EINVAL with the operator's own invalid arguments. over(): a capacity beyond
+// the int32 slots or a piece workspace below the query's value, REGNN_EUNSUPPORTED after the
+// operator's shape gate and budgets.
+struct SrcIdx {
+    const int32_t *t_ptr, *t_pos, *t_row, *t_long;
+    int64_t cap_src, n_out, cap_e;
+    float *ent, *piece_work;
+    int64_t piece_work_floats;
+    bool invalid() const {
+        return !t_ptr || !t_pos || !t_row || !t_long || !ent || !piece_work || cap_src < 0 ||
+               n_out < 0 || cap_e < 0 || piece_work_floats < 0;
+    }
+    bool over(int64_t cap_dst, int64_t HC) const {
+        return cap_e > 0x7ffffffe || cap_src > 0x7ffffffe || cap_dst > 0x7ffffffe ||
+               piece_work_floats < ns_src_work_floats(cap_e, HC);
+    }
+};
+
+// what both operators' source passes read and write; GATv2 adds xs, xd, att and has no g_el
+inline SrcArgs ns_src_args(const SrcIdx& x, const float* a, const float* gy, float slope,
+                           int64_t cap_dst, int H, int C, float* g_main, float* g_el) {
+    SrcArgs p{};
+    p.t_ptr = x.t_ptr, p.t_pos = x.t_pos, p.t_row = x.t_row, p.t_long = x.t_long;
+    p.a = a, p.ent = x.ent, p.gy = gy, p.slope = slope;
+    p.cap_src = x.cap_src, p.n_out = x.n_out, p.cap_dst = cap_dst, p.cap_e = int(x.cap_e);
+    p.max_pieces = int(ns_src_max_pieces(x.cap_e)), p.H = H, p.C = C;
+    p.g_main = g_main, p.g_el = g_el, p.work = x.piece_work;
+    return p;
+}
+
 // the three launches of the source pass
 template <bool V2>
 inline int ns_src_launch(const SrcArgs& p, hipStream_t stream) {

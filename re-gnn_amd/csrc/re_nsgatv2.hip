@@ -80,11 +80,12 @@ ns_gatv2_fwd_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__
 // g_xs -- one instruction per 64 consecutive columns of a source row (256 contiguous bytes). A row
 // of more than one chunk recomputes ga in pass 2 (the same instructions on the same operands: the
 // same bits) and carries its g_xd sums from chunk to chunk through the row it writes (the lane's
-// own stores: still one chain in entry order).
+// own stores: still one chain in entry order). The chunk fill, pass 1 and the relation bins are
+// ns_gat's (NsRow, re_nsgat_common.h); pass 2 is this operator's own.
 //
-// kGather (regnn_ns_gatv2_bwd_gather's row pass): the same instructions in the same order with the
-// atomic compiled out -- gs[e,h] goes to the per-entry scratch `ent` (0 for an entry that takes no
-// part) and g_xs is left to the source pass (re_nsgat_src.h).
+// kGather (regnn_ns_gatv2_bwd_gather's row pass): this one body with the atomic compiled out --
+// gs[e,h] goes to the per-entry scratch `ent` (0 for an entry that takes no part) and g_xs is left
+// to the source pass (re_nsgat_src.h).
 template <int T, bool kGather>
 __device__ __forceinline__ void
 ns_gatv2_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
@@ -96,24 +97,12 @@ ns_gatv2_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
                   float* __restrict__ att_slab, float* __restrict__ tab_slab,
                   float* __restrict__ ent) {
     extern __shared__ float dyn_[];            // [kWaves][n_rel * H] when tab_slab, then [H * C]
-    __shared__ float sa_[kWaves][kChunk * kMaxHeads];
-    __shared__ float sg_[kWaves][kChunk * kMaxHeads];
-    __shared__ int su_[kWaves][kChunk];
-    __shared__ int sr_[kWaves][kChunk];
-    __shared__ float sD_[kWaves][kMaxHeads];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* sa = sa_[wave];
-    float* sg = sg_[wave];
-    int* su = su_[wave];
-    int* sr = sr_[wave];
-    float* sD = sD_[wave];
+    const NsRow s = ns_row(idx, rel, tab != nullptr, xs, a, n_src, H, C);
     const int W = tab_slab ? n_rel * H : 0;
     float* bins = dyn_ + wave * W;
     float* attred = dyn_ + kWaves * W;
-    if (tab_slab) {
-        for (int i = threadIdx.x; i < kWaves * W; i += kBlock) dyn_[i] = 0.f;
-        __syncthreads();
-    }
+    if (tab_slab) ns_bins_zero(dyn_, W);
     const int HC = H * C;
     float gatt[T];
 #pragma unroll
@@ -129,59 +118,21 @@ ns_gatv2_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
         }
         const float* gyr = gy + v * HC;
         const float* xdr = xd + v * HC;
-        // the chunk [cb, cb + nc): ids, a and ga into LDS
-        auto fill = [&](int cb, int nc) {
-            wave_lds_sync();
-            for (int j = lane; j < nc; j += 64) {
-                const int u = idx[cb + j];
-                su[j] = src_ok(u, n_src) ? u : -1;
-                sr[j] = tab ? int(rel[cb + j]) : 0;
-            }
-            for (int i = lane; i < nc * H; i += 64) {
-                const int j = i / H, hh = i - j * H;
-                const int u = idx[cb + j];
-                float d = 0.f, w = 0.f;
-                if (src_ok(u, n_src)) {
-                    w = a[int64_t(cb + j) * H + hh];
-                    const float4* gp = reinterpret_cast<const float4*>(gyr + hh * C);
-                    const float4* xp = reinterpret_cast<const float4*>(
-                        xs + int64_t(u) * HC + hh * C);
-                    for (int c = 0; c < (C >> 2); ++c) {
-                        const float4 g = gp[c], x = xp[c];
-                        d = fmaf(g.x, x.x, d);
-                        d = fmaf(g.y, x.y, d);
-                        d = fmaf(g.z, x.z, d);
-                        d = fmaf(g.w, x.w, d);
-                    }
-                }
-                sa[i] = w;
-                sg[i] = d;
-            }
-            wave_lds_sync();
-        };
-        const bool one = e1 - e0 <= kChunk;
-        float D = 0.f;
+        const bool one = s.pass1(gyr, e0, e1);
         for (int cb = e0; cb < e1; cb += kChunk) {
             const int nc = min(kChunk, e1 - cb);
-            fill(cb, nc);
-            if (lane < H)
-                for (int j = 0; j < nc; ++j) D = fmaf(sa[j * H + lane], sg[j * H + lane], D);
-        }
-        if (lane < H) sD[lane] = D;
-        for (int cb = e0; cb < e1; cb += kChunk) {
-            const int nc = min(kChunk, e1 - cb);
-            if (!one) fill(cb, nc);
+            if (!one) s.fill(gyr, cb, nc);
             else wave_lds_sync();              // sD written
             for (int i = lane; i < nc * H; i += 64) {
                 const int hh = i % H;
-                sg[i] = sa[i] * (sg[i] - sD[hh]);      // gs (this lane's own slot; 0 where a is)
-                if constexpr (kGather) ent[int64_t(cb) * H + i] = sg[i];
+                s.sg[i] = s.sa[i] * (s.sg[i] - s.sD[hh]);  // gs (the lane's own slot; 0 where a is)
+                if constexpr (kGather) ent[int64_t(cb) * H + i] = s.sg[i];
             }
             wave_lds_sync();
             if (tab_slab && lane < H) {
                 for (int j = 0; j < nc; ++j) {
-                    const int r = sr[j];
-                    if (su[j] >= 0 && r < n_rel) bins[r * H + lane] += sg[j * H + lane];
+                    const int r = s.sr[j];
+                    if (s.su[j] >= 0 && r < n_rel) bins[r * H + lane] += s.sg[j * H + lane];
                 }
             }
 #pragma unroll
@@ -193,30 +144,22 @@ ns_gatv2_bwd_body(const int32_t* __restrict__ ptr, const int32_t* __restrict__ i
                 float gd = cb == e0 ? 0.f : gxdr[col];
                 float ga = gatt[t];
                 for (int j = 0; j < nc; ++j) {
-                    const int u = su[j];
+                    const int u = s.su[j];
                     if (u < 0) continue;
                     [[maybe_unused]] float* dst = g_xs + int64_t(u) * HC + col;
                     const float pre = xs[int64_t(u) * HC + col] + dv;
-                    const float gs = sg[j * H + h];
+                    const float gs = s.sg[j * H + h];
                     const float q = gs * w * (pre > 0.f ? 1.f : slope);
                     gd += q;
                     ga = fmaf(gs, pre > 0.f ? pre : pre * slope, ga);
-                    if constexpr (!kGather) unsafeAtomicAdd(dst, fmaf(sa[j * H + h], g, q));
+                    if constexpr (!kGather) unsafeAtomicAdd(dst, fmaf(s.sa[j * H + h], g, q));
                 }
                 gxdr[col] = gd;
                 gatt[t] = ga;
             }
         }
     }
-    if (tab_slab) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < W; i += kBlock) {
-            float t = dyn_[i];                 // the waves' bins in wave order
-#pragma unroll
-            for (int w = 1; w < kWaves; ++w) t += dyn_[w * W + i];
-            tab_slab[int64_t(blockIdx.x) * W + i] = t;
-        }
-    }
+    if (tab_slab) ns_bins_store(dyn_, W, tab_slab);
     if (!att_slab) return;
     for (int w = 0; w < kWaves; ++w) {         // the waves' g_att partials in wave order
         if (wave == w) {
@@ -264,6 +207,57 @@ inline int ns_gatv2_shape_rc(int32_t H, int32_t C) {
     return H * C > kMaxWidth ? REGNN_EUNSUPPORTED : REGNN_OK;
 }
 
+// Both backward entry points, as re_nsgat.hip's gat_bwd: the refusals in one order before any
+// launch, the row pass (with a slab exactly slab_rows workgroups, each writes its rows; T by the
+// row width), then the gather form's source pass. x is unread in the atomic form.
+template <bool kGather>
+inline int gatv2_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel, const float* xs,
+                     const float* xd, const float* att, const float* tab, const float* a,
+                     const float* gy, float slope, int64_t cap_dst, int64_t n_src, int32_t H,
+                     int32_t C, int32_t n_rel, float* g_xs, float* g_xd, float* att_slab,
+                     float* tab_slab, int32_t slab_rows, const SrcIdx& x, hipStream_t stream) {
+    const bool slabs = att_slab || tab_slab;
+    if (!ptr || !idx || !xs || !xd || !att || !a || !gy || !g_xs || !g_xd || (tab && !rel) ||
+        (tab_slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) ||
+        (slabs && slab_rows < 1) || (kGather && x.invalid()))
+        return REGNN_EINVAL;
+    if (const int rc = ns_gatv2_shape_rc(H, C)) return rc;
+    if ((tab_slab && int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS) ||
+        (slabs && slab_rows > REGNN_NS_GAT_WORK_FLOATS))
+        return REGNN_EUNSUPPORTED;
+    const int HC = H * C;
+    if (kGather && x.over(cap_dst, HC)) return REGNN_EUNSUPPORTED;
+    if (cap_dst > 0 || slabs) {
+        const int grid = slabs ? int(slab_rows) : ns_gat_grid(cap_dst);
+        const size_t lds = ((tab_slab ? size_t(kWaves) * n_rel * H : 0) + (att_slab ? HC : 0)) *
+                           sizeof(float);
+        auto launch = [&](auto rows_kernel, auto bwd_kernel) {
+            if constexpr (kGather) {
+                hipLaunchKernelGGL(rows_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,
+                                   rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, int(H),
+                                   int(C), int(n_rel), g_xd, att_slab, tab_slab, x.ent);
+            } else {
+                hipLaunchKernelGGL(bwd_kernel, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,
+                                   rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, int(H),
+                                   int(C), int(n_rel), g_xs, g_xd, att_slab, tab_slab);
+            }
+        };
+        if (HC <= 64) launch(ns_gatv2_bwd_rows_kernel<1>, ns_gatv2_bwd_kernel<1>);
+        else if (HC <= 128) launch(ns_gatv2_bwd_rows_kernel<2>, ns_gatv2_bwd_kernel<2>);
+        else if (HC <= 256) launch(ns_gatv2_bwd_rows_kernel<4>, ns_gatv2_bwd_kernel<4>);
+        else if (HC <= 512) launch(ns_gatv2_bwd_rows_kernel<8>, ns_gatv2_bwd_kernel<8>);
+        else if (HC <= 1024) launch(ns_gatv2_bwd_rows_kernel<16>, ns_gatv2_bwd_kernel<16>);
+        else launch(ns_gatv2_bwd_rows_kernel<32>, ns_gatv2_bwd_kernel<32>);
+        REGNN_LAUNCH_CHECK();
+    }
+    if constexpr (kGather) {
+        SrcArgs p = ns_src_args(x, a, gy, slope, cap_dst, H, C, g_xs, nullptr);
+        p.xs = xs, p.xd = xd, p.att = att;
+        return ns_src_launch<true>(p, stream);
+    }
+    return REGNN_OK;
+}
+
 }  // namespace
 }  // namespace regnn
 
@@ -296,34 +290,8 @@ extern "C" int regnn_ns_gatv2_bwd(const int32_t* ptr, const int32_t* idx, const 
                                   int64_t cap_dst, int64_t n_src, int32_t H, int32_t C,
                                   int32_t n_rel, float* g_xs, float* g_xd, float* att_slab,
                                   float* tab_slab, int32_t slab_rows, hipStream_t stream) {
-    const bool slabs = att_slab || tab_slab;
-    if (!ptr || !idx || !xs || !xd || !att || !a || !gy || !g_xs || !g_xd || (tab && !rel) ||
-        (tab_slab && !tab) || cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) ||
-        (slabs && slab_rows < 1))
-        return REGNN_EINVAL;
-    if (const int rc = ns_gatv2_shape_rc(H, C)) return rc;
-    if ((tab_slab && int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS) ||
-        (slabs && slab_rows > REGNN_NS_GAT_WORK_FLOATS))
-        return REGNN_EUNSUPPORTED;
-    if (cap_dst == 0 && !slabs) return REGNN_OK;
-    // with a slab the launch has exactly slab_rows workgroups: each writes its rows
-    const int grid = slabs ? int(slab_rows) : ns_gat_grid(cap_dst);
-    const int HC = H * C;
-    const size_t lds = ((tab_slab ? size_t(kWaves) * n_rel * H : 0) + (att_slab ? HC : 0)) *
-                       sizeof(float);
-#define REGNN_NS_GATV2_BWD(T)                                                                    \
-    hipLaunchKernelGGL(ns_gatv2_bwd_kernel<T>, dim3(grid), dim3(kBlock), lds, stream, ptr, idx,  \
-                       rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, int(H), int(C),      \
-                       int(n_rel), g_xs, g_xd, att_slab, tab_slab)
-    if (HC <= 64) REGNN_NS_GATV2_BWD(1);
-    else if (HC <= 128) REGNN_NS_GATV2_BWD(2);
-    else if (HC <= 256) REGNN_NS_GATV2_BWD(4);
-    else if (HC <= 512) REGNN_NS_GATV2_BWD(8);
-    else if (HC <= 1024) REGNN_NS_GATV2_BWD(16);
-    else REGNN_NS_GATV2_BWD(32);
-#undef REGNN_NS_GATV2_BWD
-    REGNN_LAUNCH_CHECK();
-    return REGNN_OK;
+    return gatv2_bwd<false>(ptr, idx, rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, H, C,
+                            n_rel, g_xs, g_xd, att_slab, tab_slab, slab_rows, SrcIdx{}, stream);
 }
 
 extern "C" int regnn_ns_gatv2_bwd_gather(
@@ -334,43 +302,8 @@ extern "C" int regnn_ns_gatv2_bwd_gather(
     const int32_t* t_pos, const int32_t* t_row, const int32_t* t_long, int64_t cap_src,
     int64_t n_out, int64_t cap_e, float* ent, float* piece_work, int64_t piece_work_floats,
     hipStream_t stream) {
-    const bool slabs = att_slab || tab_slab;
-    if (!ptr || !idx || !xs || !xd || !att || !a || !gy || !g_xs || !g_xd || !t_ptr || !t_pos ||
-        !t_row || !t_long || !ent || !piece_work || (tab && !rel) || (tab_slab && !tab) ||
-        cap_dst < 0 || n_src < 0 || n_rel < 0 || (tab && n_rel < 1) || (slabs && slab_rows < 1) ||
-        cap_src < 0 || n_out < 0 || cap_e < 0 || piece_work_floats < 0)
-        return REGNN_EINVAL;
-    if (const int rc = ns_gatv2_shape_rc(H, C)) return rc;
-    if ((tab_slab && int64_t(n_rel) * H > REGNN_NS_GAT_MAX_BINS) ||
-        (slabs && slab_rows > REGNN_NS_GAT_WORK_FLOATS))
-        return REGNN_EUNSUPPORTED;
-    const int HC = H * C;
-    if (cap_e > 0x7ffffffe || cap_src > 0x7ffffffe || cap_dst > 0x7ffffffe ||
-        piece_work_floats < ns_src_work_floats(cap_e, HC))
-        return REGNN_EUNSUPPORTED;
-    if (cap_dst > 0 || slabs) {
-        // with a slab the launch has exactly slab_rows workgroups: each writes its rows
-        const int grid = slabs ? int(slab_rows) : ns_gat_grid(cap_dst);
-        const size_t lds = ((tab_slab ? size_t(kWaves) * n_rel * H : 0) + (att_slab ? HC : 0)) *
-                           sizeof(float);
-#define REGNN_NS_GATV2_ROWS(T)                                                                   \
-    hipLaunchKernelGGL(ns_gatv2_bwd_rows_kernel<T>, dim3(grid), dim3(kBlock), lds, stream, ptr,  \
-                       idx, rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, int(H), int(C), \
-                       int(n_rel), g_xd, att_slab, tab_slab, ent)
-        if (HC <= 64) REGNN_NS_GATV2_ROWS(1);
-        else if (HC <= 128) REGNN_NS_GATV2_ROWS(2);
-        else if (HC <= 256) REGNN_NS_GATV2_ROWS(4);
-        else if (HC <= 512) REGNN_NS_GATV2_ROWS(8);
-        else if (HC <= 1024) REGNN_NS_GATV2_ROWS(16);
-        else REGNN_NS_GATV2_ROWS(32);
-#undef REGNN_NS_GATV2_ROWS
-        REGNN_LAUNCH_CHECK();
-    }
-    SrcArgs p{};
-    p.t_ptr = t_ptr, p.t_pos = t_pos, p.t_row = t_row, p.t_long = t_long;
-    p.a = a, p.ent = ent, p.gy = gy, p.xs = xs, p.xd = xd, p.att = att, p.slope = slope;
-    p.cap_src = cap_src, p.n_out = n_out, p.cap_dst = cap_dst, p.cap_e = int(cap_e);
-    p.max_pieces = int(ns_src_max_pieces(cap_e)), p.H = H, p.C = C;
-    p.g_main = g_xs, p.g_el = nullptr, p.work = piece_work;
-    return ns_src_launch<true>(p, stream);
+    const SrcIdx x{t_ptr, t_pos, t_row, t_long, cap_src, n_out, cap_e, ent, piece_work,
+                   piece_work_floats};
+    return gatv2_bwd<true>(ptr, idx, rel, xs, xd, att, tab, a, gy, slope, cap_dst, n_src, H, C,
+                           n_rel, g_xs, g_xd, att_slab, tab_slab, slab_rows, x, stream);
 }

@@ -26,6 +26,10 @@ I64 = ctypes.c_int64
 U64 = ctypes.c_uint64
 F32 = ctypes.c_float
 
+# regnn_ns_gat*_bwd*: what all four take up to slab_rows; the gather forms' index and workspaces
+_NS_BWD = [P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P, I32]
+_NS_IDX = [P, P, P, P, I64, I64, I64, P, P, I64]
+
 _SIG = {
     "regnn_abi_version": ([], ctypes.c_int),
     "regnn_gemm_x6_work_floats": ([I64, I64, I32], I64),
@@ -116,21 +120,16 @@ _SIG = {
     "regnn_ns_spmm_bwd_csc": ([P, P, P, P, P, P, P, P, P, I32, P, I32, I64, I32, I32, P, P],
                               ctypes.c_int),
     "regnn_ns_gat_fwd": ([P, P, P, P, P, P, P, F32, I64, I64, I32, I32, P, P, P, P], ctypes.c_int),
-    "regnn_ns_gat_bwd": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P,
-                          I32, P], ctypes.c_int),
+    "regnn_ns_gat_bwd": (_NS_BWD + [P], ctypes.c_int),
     "regnn_ns_gatv2_fwd": ([P, P, P, P, P, P, P, F32, I64, I64, I32, I32, P, P, P, P],
                            ctypes.c_int),
-    "regnn_ns_gatv2_bwd": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P, P,
-                            I32, P], ctypes.c_int),
+    "regnn_ns_gatv2_bwd": (_NS_BWD + [P], ctypes.c_int),
     "regnn_ns_tidx_long_ints": ([I64], I64),
     "regnn_ns_tidx_work_ints": ([I64, I64], I64),
     "regnn_ns_block_tidx": ([P, P, I64, I64, I64, I64, P, P, P, P, I64, P, I64, P], ctypes.c_int),
     "regnn_ns_gat_src_work_floats": ([I64, I32], I64),
-    "regnn_ns_gat_bwd_gather": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P, P,
-                                 P, I32, P, P, P, P, I64, I64, I64, P, P, I64, P], ctypes.c_int),
-    "regnn_ns_gatv2_bwd_gather": ([P, P, P, P, P, P, P, P, P, F32, I64, I64, I32, I32, I32, P, P,
-                                   P, P, I32, P, P, P, P, I64, I64, I64, P, P, I64, P],
-                                  ctypes.c_int),
+    "regnn_ns_gat_bwd_gather": (_NS_BWD + _NS_IDX + [P], ctypes.c_int),
+    "regnn_ns_gatv2_bwd_gather": (_NS_BWD + _NS_IDX + [P], ctypes.c_int),
     "regnn_mag_attn_fwd": ([P, P, P, P, I32, P, P, P, P, P, P, P, P, I64, I32, I32, F32, P, P],
                            ctypes.c_int),
     "regnn_mag_attn_epilogue": ([P, P, P, P, F32, P, P, P, P, F32, I32, I64, I32, I32, P, P],

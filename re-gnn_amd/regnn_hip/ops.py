@@ -773,19 +773,35 @@ def ns_gat_bytes(E, n_dst, H, C, kind):
     return E * (5 + 16 * H + 8 * H * C) + n_dst * (4 + 8 * H + 4 * H * C)
 
 
+def _ns_attn_check(op, blk, **tensors):
+    """what both sampled-block attention forwards refuse first: fp32 only, the CSR layout only"""
+    for name, t in tensors.items():
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{op}: {name} is {t.dtype}; the sampled-block attention runs on fp32")
+    if getattr(blk, "strided_rows", None) is not None:
+        raise ValueError(f"{op} reads the CSR layout; this block was sampled in the "
+                         "fixed-stride layout (strided_rows)")
+
+
+def _ns_attn_buffers(blk, H, C, device):
+    """(a [capacity entries, H], out [n_dst, H, C], work) of a sampled-block attention forward"""
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.empty(blk.csr_idx.numel(), H, **f32), torch.empty(blk.n_dst, H, C, **f32),
+            torch.empty(NS_GAT_WORK_FLOATS, **f32))
+
+
+def _ns_slab_rows(blk):
+    """workgroups (= slab rows) of a sampled-block attention backward that fills a slab"""
+    return max(1, min(NS_GAT_BWD_ROWS["n"], NS_GAT_WORK_FLOATS, -(-blk.n_dst // 4)))
+
+
 class _NsGat(torch.autograd.Function):
     """(out, a) of regnn_ns_gat_fwd over a device-sampled block in the CSR layout; backward
     regnn_ns_gat_bwd (+ regnn_rel_reduce for the relation table). a is not differentiable."""
 
     @staticmethod
     def forward(ctx, el, er, tab, ft, blk, slope):
-        for name, t in (("el", el), ("er", er), ("tab", tab), ("ft", ft)):
-            if t is not None and t.dtype != torch.float32:
-                raise TypeError(f"ns_gat: {name} is {t.dtype}; the sampled-block attention runs "
-                                "on fp32")
-        if getattr(blk, "strided_rows", None) is not None:
-            raise ValueError("ns_gat reads the CSR layout; this block was sampled in the "
-                             "fixed-stride layout (strided_rows)")
+        _ns_attn_check("ns_gat", blk, el=el, er=er, tab=tab, ft=ft)
         if ft.dim() != 3 or el.dim() != 2 or er.dim() != 2:
             raise ValueError("ns_gat: ft [n, H, C], el [n, H], er [n_dst, H]")
         H, C = int(ft.shape[1]), int(ft.shape[2])
@@ -796,9 +812,7 @@ class _NsGat(torch.autograd.Function):
         el, er, ft = el.contiguous(), er.contiguous(), ft.contiguous()
         t = None if tab is None else tab.detach().contiguous()
         n_src = min(int(ft.shape[0]), blk.n_src)
-        a = torch.empty(blk.csr_idx.numel(), H, dtype=torch.float32, device=ft.device)
-        out = torch.empty(blk.n_dst, H, C, dtype=torch.float32, device=ft.device)
-        work = torch.empty(NS_GAT_WORK_FLOATS, dtype=torch.float32, device=ft.device)
+        a, out, work = _ns_attn_buffers(blk, H, C, ft.device)
         with timed("ns_gat_fwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "fwd")):
             L.call("regnn_ns_gat_fwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
                    L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
@@ -817,31 +831,21 @@ class _NsGat(torch.autograd.Function):
         blk = ctx.blk
         H, C = int(ft.shape[1]), int(ft.shape[2])
         gy = gy.contiguous().float()
-        if gather:                             # every row written by the source pass
-            g_ft, g_el = torch.empty_like(ft), torch.empty_like(el)
-        else:
-            g_ft, g_el = torch.zeros_like(ft), torch.zeros_like(el)  # the atomics' targets
-        g_er = torch.empty_like(er)
+        # (gather: every row written by the source pass; else the atomics' targets)
+        new = torch.empty_like if gather else torch.zeros_like
+        g_ft, g_el, g_er = new(ft), new(el), torch.empty_like(er)
         n_rel = int(t.shape[0]) if t is not None else 0
         slab, rows = None, 0
         if t is not None and ctx.needs_input_grad[2]:
-            rows = max(1, min(NS_GAT_BWD_ROWS["n"], NS_GAT_WORK_FLOATS, -(-blk.n_dst // 4)))
+            rows = _ns_slab_rows(blk)
             slab = torch.empty(rows, n_rel * H, dtype=torch.float32, device=ft.device)
-        if gather:
-            extra, _keep = _gat_src_args(blk, ft.shape[0], H, C, ft.device)
-            with timed("ns_gat_bwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "bwd")):
-                L.call("regnn_ns_gat_bwd_gather", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
-                       L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
-                       L.ptr(ft), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C,
-                       n_rel, L.ptr(g_ft), L.ptr(g_el), L.ptr(g_er), L.ptr(slab), rows, *extra,
-                       L.stream())
-            g_tab = _reduce(slab, n_rel * H).view(ctx.tab_shape) if slab is not None else None
-            return g_el, g_er, g_tab, g_ft, None, None
+        extra, _keep = _gat_src_args(blk, ft.shape[0], H, C, ft.device) if gather else ((), None)
         with timed("ns_gat_bwd", ns_gat_bytes(blk.E, blk.n_dst, H, C, "bwd")):
-            L.call("regnn_ns_gat_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
-                   L.ptr(blk.rel if t is not None else None), L.ptr(el), L.ptr(er), L.ptr(t),
-                   L.ptr(ft), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C, n_rel,
-                   L.ptr(g_ft), L.ptr(g_el), L.ptr(g_er), L.ptr(slab), rows, L.stream())
+            L.call("regnn_ns_gat_bwd" + ("_gather" if gather else ""), L.ptr(blk.csr_ptr),
+                   L.ptr(blk.csr_idx), L.ptr(blk.rel if t is not None else None), L.ptr(el),
+                   L.ptr(er), L.ptr(t), L.ptr(ft), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst,
+                   ctx.n_src, H, C, n_rel, L.ptr(g_ft), L.ptr(g_el), L.ptr(g_er), L.ptr(slab),
+                   rows, *extra, L.stream())
         g_tab = _reduce(slab, n_rel * H).view(ctx.tab_shape) if slab is not None else None
         return g_el, g_er, g_tab, g_ft, None, None
 
@@ -883,13 +887,7 @@ class _NsGatv2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xs, xd, att, tab, blk, slope):
-        for name, t in (("xs", xs), ("xd", xd), ("att", att), ("tab", tab)):
-            if t is not None and t.dtype != torch.float32:
-                raise TypeError(f"ns_gatv2: {name} is {t.dtype}; the sampled-block attention "
-                                "runs on fp32")
-        if getattr(blk, "strided_rows", None) is not None:
-            raise ValueError("ns_gatv2 reads the CSR layout; this block was sampled in the "
-                             "fixed-stride layout (strided_rows)")
+        _ns_attn_check("ns_gatv2", blk, xs=xs, xd=xd, att=att, tab=tab)
         if xs.dim() != 3 or xd.dim() != 3:
             raise ValueError("ns_gatv2: xs [n, H, C], xd [n_dst, H, C]")
         H, C = int(xs.shape[1]), int(xs.shape[2])
@@ -901,9 +899,7 @@ class _NsGatv2(torch.autograd.Function):
         xs, xd, w = xs.contiguous(), xd.contiguous(), att.detach().contiguous()
         t = None if tab is None else tab.detach().contiguous()
         n_src = min(int(xs.shape[0]), blk.n_src)
-        a = torch.empty(blk.csr_idx.numel(), H, dtype=torch.float32, device=xs.device)
-        out = torch.empty(blk.n_dst, H, C, dtype=torch.float32, device=xs.device)
-        work = torch.empty(NS_GAT_WORK_FLOATS, dtype=torch.float32, device=xs.device)
+        a, out, work = _ns_attn_buffers(blk, H, C, xs.device)
         with timed("ns_gatv2_fwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "fwd")):
             L.call("regnn_ns_gatv2_fwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
                    L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
@@ -932,27 +928,18 @@ class _NsGatv2(torch.autograd.Function):
         att_slab = tab_slab = None
         rows = 0
         if need_att or need_tab:
-            rows = max(1, min(NS_GAT_BWD_ROWS["n"], NS_GAT_WORK_FLOATS, -(-blk.n_dst // 4)))
+            rows = _ns_slab_rows(blk)
             if need_att:
                 att_slab = torch.empty(rows, H * C, dtype=torch.float32, device=xs.device)
             if need_tab:
                 tab_slab = torch.empty(rows, n_rel * H, dtype=torch.float32, device=xs.device)
-        if gather:
-            extra, _keep = _gat_src_args(blk, xs.shape[0], H, C, xs.device)
-            with timed("ns_gatv2_bwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "bwd")):
-                L.call("regnn_ns_gatv2_bwd_gather", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
-                       L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
-                       L.ptr(t), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C,
-                       n_rel, L.ptr(g_xs), L.ptr(g_xd), L.ptr(att_slab), L.ptr(tab_slab), rows,
-                       *extra, L.stream())
-            g_att = _reduce(att_slab, H * C).view(ctx.att_shape) if need_att else None
-            g_tab = _reduce(tab_slab, n_rel * H).view(ctx.tab_shape) if need_tab else None
-            return g_xs, g_xd, g_att, g_tab, None, None
+        extra, _keep = _gat_src_args(blk, xs.shape[0], H, C, xs.device) if gather else ((), None)
         with timed("ns_gatv2_bwd", ns_gatv2_bytes(blk.E, blk.n_dst, H, C, "bwd")):
-            L.call("regnn_ns_gatv2_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
-                   L.ptr(blk.rel if t is not None else None), L.ptr(xs), L.ptr(xd), L.ptr(w),
-                   L.ptr(t), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst, ctx.n_src, H, C, n_rel,
-                   L.ptr(g_xs), L.ptr(g_xd), L.ptr(att_slab), L.ptr(tab_slab), rows, L.stream())
+            L.call("regnn_ns_gatv2_bwd" + ("_gather" if gather else ""), L.ptr(blk.csr_ptr),
+                   L.ptr(blk.csr_idx), L.ptr(blk.rel if t is not None else None), L.ptr(xs),
+                   L.ptr(xd), L.ptr(w), L.ptr(t), L.ptr(a), L.ptr(gy), ctx.slope, blk.n_dst,
+                   ctx.n_src, H, C, n_rel, L.ptr(g_xs), L.ptr(g_xd), L.ptr(att_slab),
+                   L.ptr(tab_slab), rows, *extra, L.stream())
         g_att = _reduce(att_slab, H * C).view(ctx.att_shape) if need_att else None
         g_tab = _reduce(tab_slab, n_rel * H).view(ctx.tab_shape) if need_tab else None
         return g_xs, g_xd, g_att, g_tab, None, None
@@ -970,10 +957,10 @@ def ns_gatv2(blk, xs, xd, att, tab, slope=0.2, return_attn=False):
     multiple of 4 in [4, 512], H * C <= 2048. The backward is the global-max softmax's with the
     maximum a constant; g_xd, g_att and g_tab are summed in a fixed order, g_xs by float atomics
     (regnn_ns_gatv2_bwd) or, with NS_GAT_SRC "gather", by a walk over the block's transposed index
-    (regnn_ns_gatv2_bwd_gather: the same bits on every run). return_attn: also a [blk capacity entries, H] (no gradient)."""
+    (regnn_ns_gatv2_bwd_gather: the same bits on every run).
+    return_attn: also a [blk capacity entries, H] (no gradient)."""
     out, a = _NsGatv2.apply(xs, xd, att, tab, blk, slope)
     return (out, a) if return_attn else out
-
 
 
 class _NsTypedAgg(torch.autograd.Function):
