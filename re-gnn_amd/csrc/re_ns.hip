@@ -177,11 +177,9 @@ ns_sample_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ id
 // CSR position, target row, the dedup candidate (first-seen order over the slots = the CSR order
 // restricted to the edges); meta-only (lean): the source's type / table row instead. Edge counts
 // are added per block into sizes[8 + hop] (zeroed by ns_batch_kernel / set_targets) and state[5].
-// G lanes per target: 64, or 32 (two targets per wave) when the row's k + 1 slots fit in 32 lanes
-// (fan-outs <= 31: half the waves and half the sampling instructions of a hop)
+// One wave per target (k + 1 <= 64 slots, a lane each).
 constexpr int kNsStrWaves = 16;            // waves per block
 
-template <int G>
 __global__ void __launch_bounds__(64 * kNsStrWaves)
 ns_sample_strided_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
                          const uint8_t* __restrict__ etype, const int32_t* __restrict__ ntype,
@@ -194,12 +192,10 @@ ns_sample_strided_kernel(const int32_t* __restrict__ ptr, const int32_t* __restr
                          int32_t* __restrict__ blk_row, float* __restrict__ inv,
                          const int64_t* __restrict__ local, int32_t* __restrict__ e_type,
                          int64_t* __restrict__ e_off, int lean, int32_t* __restrict__ csc_cnt) {
-    constexpr int TPW = 64 / G;                // targets per wave
-    __shared__ int wsum[kNsStrWaves * TPW];
-    const int wl = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int lane = wl % G, tl = wv * TPW + wl / G;   // lane within the target's group
-    const uint64_t gmask = G == 64 ? ~0ull : (0xFFFFFFFFull << (wl & 32));
-    const int i = blockIdx.x * (kNsStrWaves * TPW) + tl;
+    constexpr int G = 64;                      // lanes per target
+    __shared__ int wsum[kNsStrWaves];
+    const int lane = threadIdx.x & 63, tl = threadIdx.x >> 6;   // lane of the target's wave
+    const int i = blockIdx.x * kNsStrWaves + tl;
     const int n = sizes[hop];
     const int S = k + 1;
     const int64_t base = int64_t(i) * S;
@@ -231,7 +227,7 @@ ns_sample_strided_kernel(const int32_t* __restrict__ ptr, const int32_t* __restr
                                                uint64_t(jl + 1)) >> 32) : 0;
             for (int i = 0; i < k; ++i) {
                 const int pos = __shfl(my_pos, i, G);
-                const bool seen = (__ballot(slot == pos) & gmask) != 0;
+                const bool seen = __ballot(slot == pos) != 0;
                 if (lane == i) slot = seen ? d - k + i : pos;
             }
             rank = 0;
@@ -284,7 +280,7 @@ ns_sample_strided_kernel(const int32_t* __restrict__ ptr, const int32_t* __restr
     if (threadIdx.x == 0) {
         int e = 0;
 #pragma unroll
-        for (int q = 0; q < kNsStrWaves * TPW; ++q) e += wsum[q];
+        for (int q = 0; q < kNsStrWaves; ++q) e += wsum[q];
         if (e) {
             atomicAdd(sizes + 8 + hop, e);
             atomicAdd(reinterpret_cast<unsigned long long*>(state + 5), (unsigned long long)e);
@@ -1539,15 +1535,6 @@ xent_bwd_colsum_kernel(const float* __restrict__ z, const int64_t* __restrict__ 
 
 using namespace regnn;
 
-// two targets per wave in the strided sampler: REGNN_NS_HALF_WAVES=1 (off by default — measured
-// 136.6 vs 135.0 us per fused step at hidden 64: the sampler runs beside the model, and its
-// instruction count is not what the step waits on)
-static bool ns_half_waves() {
-    const char* v = getenv("REGNN_NS_HALF_WAVES");   // read per launch: tests switch it
-    return v && v[0] == '1';
-}
-
-
 extern "C" {
 
 int64_t regnn_ns_csc_hub_work_floats(int32_t F) {
@@ -1722,20 +1709,12 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
     }
     if (strided) {
         // sampling + placement in one launch, no row-offset scan (the layout above)
-        if (k + 1 <= 32 && ns_half_waves())
-            hipLaunchKernelGGL(ns_sample_strided_kernel<32>,
-                               dim3(unsigned((cap_dst + 2 * kNsStrWaves - 1) / (2 * kNsStrWaves))),
-                               dim3(64 * kNsStrWaves), 0, stream, ptr, idx, etype, ntype,
-                               num_edge_types, n_id, sizes, hop, cap_dst, k, state, g2l, first,
-                               scnt, gsrc, blk_idx, blk_rel, blk_pos, blk_row, inv, local,
-                               edge_type, edge_off, lean, csc_cnt);
-        else
-            hipLaunchKernelGGL(ns_sample_strided_kernel<64>,
-                               dim3(unsigned((cap_dst + kNsStrWaves - 1) / kNsStrWaves)),
-                               dim3(64 * kNsStrWaves), 0, stream, ptr, idx, etype, ntype,
-                               num_edge_types, n_id, sizes, hop, cap_dst, k, state, g2l, first,
-                               scnt, gsrc, blk_idx, blk_rel, blk_pos, blk_row, inv, local,
-                               edge_type, edge_off, lean, csc_cnt);
+        hipLaunchKernelGGL(ns_sample_strided_kernel,
+                           dim3(unsigned((cap_dst + kNsStrWaves - 1) / kNsStrWaves)),
+                           dim3(64 * kNsStrWaves), 0, stream, ptr, idx, etype, ntype,
+                           num_edge_types, n_id, sizes, hop, cap_dst, k, state, g2l, first,
+                           scnt, gsrc, blk_idx, blk_rel, blk_pos, blk_row, inv, local,
+                           edge_type, edge_off, lean, csc_cnt);
         REGNN_LAUNCH_CHECK();
         if (lean) return REGNN_OK;
         const int ce = int(cap_e);

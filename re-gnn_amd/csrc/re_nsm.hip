@@ -1647,10 +1647,9 @@ int regnn_nsm_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStream
             hipLaunchKernelGGL((agg0_kernel<KK, NN, RS>), dim3(grid), dim3(kBlock), lds, stream, A); \
             REGNN_LAUNCH_CHECK();                                                              \
         } else
-        AGG0_CASE(128, 4, true) AGG0_CASE(128, MT, true) AGG0_CASE(64, 4, true)
-        AGG0_CASE(64, MT, true) AGG0_CASE(128, 4, false) AGG0_CASE(128, MT, false)
-        AGG0_CASE(64, 4, false) AGG0_CASE(64, MT, false)
-            return REGNN_EUNSUPPORTED;
+        AGG0_CASE(128, 4, true) AGG0_CASE(64, 4, true) AGG0_CASE(64, MT, true)
+        AGG0_CASE(128, 4, false) AGG0_CASE(64, 4, false) AGG0_CASE(64, MT, false)
+            return REGNN_EUNSUPPORTED;     // (no (128, MT) form: T (K + 1) <= 600 above, so T <= 4)
 #undef AGG0_CASE
     }
     // 3. layers 1 .. L-2

@@ -36,28 +36,17 @@
 #include "re_nsm_common.h"
 #include "re_csc_place.h"
 
-#include <cstdlib>
-
 namespace regnn {
 namespace nsm2 {
 using namespace regnn::nsm;
 
 constexpr int kRows = 16;                  // target rows per block (one MFMA row tile)
-// bwd0 blocks per node type and gather blocks (the slab layout follows them). The defaults are
-// the measured choice; REGNN_NSM_BWD_BLOCKS / REGNN_NSM_GATH_BLOCKS override them for A/B runs
-// (read once per process, so regnn_nsm_slab_floats and regnn_nsm_step agree).
-inline int env_blocks(const char* name, int dflt) {
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : 0;
-    return v >= 16 && v <= 4096 ? v : dflt;
-}
-static const int kBwdBlocks = env_blocks("REGNN_NSM_BWD_BLOCKS", 128);   // wave groups per type
-// bwd0's wave groups per block (REGNN_NSM_BWD_GROUPS, 1 or 2): two groups in half the blocks
-// (one 512-thread block per CU) share the W_t image and sum their partials in LDS
-static const int kBwdGroups = [] {
-    const char* e = getenv("REGNN_NSM_BWD_GROUPS");
-    return e && e[0] == '1' ? 1 : 2;
-}();
+// bwd0 wave groups per node type and gather blocks (kGathBlocks, below): the measured choices
+// (DESIGN §4b); the slab layout and the launches follow the same constants.
+constexpr int kBwdBlocks = 128;            // wave groups per type
+// bwd0's wave groups per block: two groups in half the blocks (one 512-thread block per CU)
+// share the W_t image and sum their partials in LDS
+constexpr int kBwdGroups = 2;
 constexpr int kMaxCT = 27;                 // class tiles of 16 (the head's LDS holds C <= 384)
 constexpr float kFixScale = 1099511627776.0f;      // 2^40: fixed point of layer 1's scatter
 constexpr float kFixInv = 9.094947017729282e-13f;  // 2^-40
@@ -1207,7 +1196,7 @@ struct GathArgs {
 constexpr int kGathT = 512, kGathG = kGathT / 16;
 // 192 blocks: 104.3-104.9 us per step against 105.7-106.2 at 256, 106.0-106.7 at 160, 106.6-107.0
 // at 128 (round 5, lookahead 32: fewer gather blocks beside the sampler's launches)
-static const int kGathBlocks = env_blocks("REGNN_NSM_GATH_BLOCKS", 192);
+constexpr int kGathBlocks = 192;
 
 constexpr int kGathW = 4 * F;
 constexpr int kShort = 16;                 // = re_ns.hip kCscShort
@@ -1512,23 +1501,24 @@ constexpr size_t bwd0_group_floats(int n_rel) {
     return size_t(16) * (K + 4) * (RS ? 2 : 1) + 16 * (F + 16) + 16 * (F + 4) + 2 * 16 * 68 +
            16 * 4 + 16 * 2 + 4 * 16 * 2 + size_t(n_rel) * 16;
 }
-template <int K, bool RS, int NG>
+template <int K, bool RS>
 constexpr size_t bwd0_lds_floats(int n_rel) {
-    return size_t(K) * (F + 4) + 2 * F + NG * bwd0_group_floats<K, RS>(n_rel);
+    return size_t(K) * (F + 4) + 2 * F + kBwdGroups * bwd0_group_floats<K, RS>(n_rel);
 }
 
-// NG wave groups of 4 waves per block: group g takes tiles NG b + g, NG (b + grid) + g, ..; the
-// groups' W_t image is shared and their partials meet in LDS (group 0 + group 1, fixed order)
-// before one slab row per block: NG = 2 with half the blocks keeps the waves per CU and halves
-// the split-K slab finalize reads.
+// NG = kBwdGroups = 2 wave groups of 4 waves per block: group g takes tiles NG b + g,
+// NG (b + grid) + g, ..; the groups' W_t image is shared and their partials meet in LDS (group 0
+// + group 1, fixed order) before one slab row per block: two groups in half the blocks keep the
+// waves per CU and halve the split-K slab finalize reads.
 // RES (residual with relation slots; an instantiation of its own, as agg0w's): the re-formed
 // S = wr U + ws x_self takes agg0's ws = tab[r_self] + cnt_v (cnt_v = the row's slot counts + 1);
 // the relation bins keep tab[r_self]'s own gradient. The edge pass reads s_agg / s_w, which carry
 // the residual part already
-template <int K, bool RS, int NG, bool RES = false>
-__global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
+template <int K, bool RS, bool RES = false>
+__global__ void __launch_bounds__(kBlock * kBwdGroups) bwd0_kernel(Bwd0Args A) {
     static_assert(!RES || RS, "the edge pass's sums carry the residual part");
-    static_assert(NG == 1 || NG == 2, "one or two wave groups");
+    constexpr int NG = kBwdGroups;
+    static_assert(NG == 2, "the partials meet as group 0 + group 1");
     constexpr int XS = K + 4, GS = F + 16, G2 = F + 4, WS = F + 4;
     constexpr int KB = K / 64;                // k blocks per wave
     constexpr int XV = K / 4 * 16 / kBlock;   // float4 per thread per 16-row tile of a K-wide row
@@ -1542,7 +1532,7 @@ __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
     if (A.adam_step && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) A.adam_step[0] += 1;
     float* bc = Wk + K * WS;                  // [F] b_t
     float* tabl = bc + F;                     // [F]
-    const int grp = NG == 1 ? 0 : int(threadIdx.x) / kBlock;
+    const int grp = int(threadIdx.x) / kBlock;
     const int tid = int(threadIdx.x) - grp * kBlock;
     float* gbase = tabl + F + grp * bwd0_group_floats<K, RS>(A.n_rel);
     float* ush = gbase;                       // [16][XS] U_t (RS) or S_t
@@ -1780,39 +1770,37 @@ __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
         }
     }
     PH(2, 2);
-    if constexpr (NG == 2) {
-        // group 1's partials into LDS (W_t partial over Wk, the rest over its tile buffers),
-        // group 0 adds them to its own: one slab row per block
-        float* xg = tabl + F + bwd0_group_floats<K, RS>(A.n_rel);   // group 1's region
-        float* x0 = xg + 4 * 64 * 16;          // after its W_0 partial: the bias partial
-        __syncthreads();                       // every group done with Wk
-        if (grp == 1) {
-#pragma unroll
-            for (int a = 0; a < KB; ++a)
-#pragma unroll
-                for (int jb = 0; jb < 4; ++jb)
-                    *reinterpret_cast<f32x4*>(Wk + ((w * KB + a) * 4 + jb) * 256 + 4 * lane) = acc[a][jb];
-            if (t0) {
-#pragma unroll
-                for (int jb = 0; jb < 4; ++jb)
-                    *reinterpret_cast<f32x4*>(xg + (w * 4 + jb) * 256 + 4 * lane) = acc0[jb];
-            }
-            if (tid < F) x0[tid] = bsum;
-        }
-        __syncthreads();
-        if (grp == 1) return;                  // (no barrier follows)
+    // group 1's partials into LDS (W_t partial over Wk, the rest over its tile buffers),
+    // group 0 adds them to its own: one slab row per block
+    float* xg = tabl + F + bwd0_group_floats<K, RS>(A.n_rel);   // group 1's region
+    float* x0 = xg + 4 * 64 * 16;             // after its W_0 partial: the bias partial
+    __syncthreads();                          // every group done with Wk
+    if (grp == 1) {
 #pragma unroll
         for (int a = 0; a < KB; ++a)
 #pragma unroll
             for (int jb = 0; jb < 4; ++jb)
-                acc[a][jb] += *reinterpret_cast<const f32x4*>(Wk + ((w * KB + a) * 4 + jb) * 256 + 4 * lane);
+                *reinterpret_cast<f32x4*>(Wk + ((w * KB + a) * 4 + jb) * 256 + 4 * lane) = acc[a][jb];
         if (t0) {
 #pragma unroll
             for (int jb = 0; jb < 4; ++jb)
-                acc0[jb] += *reinterpret_cast<const f32x4*>(xg + (w * 4 + jb) * 256 + 4 * lane);
+                *reinterpret_cast<f32x4*>(xg + (w * 4 + jb) * 256 + 4 * lane) = acc0[jb];
         }
-        if (tid < F) bsum += x0[tid];
+        if (tid < F) x0[tid] = bsum;
     }
+    __syncthreads();
+    if (grp == 1) return;                     // (no barrier follows)
+#pragma unroll
+    for (int a = 0; a < KB; ++a)
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+            acc[a][jb] += *reinterpret_cast<const f32x4*>(Wk + ((w * KB + a) * 4 + jb) * 256 + 4 * lane);
+    if (t0) {
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+            acc0[jb] += *reinterpret_cast<const f32x4*>(xg + (w * 4 + jb) * 256 + 4 * lane);
+    }
+    if (tid < F) bsum += x0[tid];
     // ---- partials: g W_t as [64][K] (lins[t].weight's layout), g b_t
     float* o = A.slab + (int64_t(t) * gridDim.x + blockIdx.x) * int64_t((K + 1) * F);
 #pragma unroll
@@ -1832,13 +1820,12 @@ __global__ void __launch_bounds__(kBlock * NG) bwd0_kernel(Bwd0Args A) {
             if (tid < A.n_rel) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sr += bins[tid * 16 + r];
-                if constexpr (NG == 2) {       // group 1's bins, added after group 0's
-                    const float* bins1 = bins + bwd0_group_floats<K, RS>(A.n_rel);
-                    float s1 = 0.f;
+                // group 1's bins, added after group 0's
+                const float* bins1 = bins + bwd0_group_floats<K, RS>(A.n_rel);
+                float s1 = 0.f;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) s1 += bins1[tid * 16 + r];
-                    sr += s1;
-                }
+                for (int r = 0; r < 16; ++r) s1 += bins1[tid * 16 + r];
+                sr += s1;
             }
             A.rslab[(int64_t(t) * gridDim.x + blockIdx.x) * F + tid] = sr;
         }
@@ -2303,7 +2290,10 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         A.residual = p->residual;
         int grid = (w->cap[h] + 15) / 16;
         if (pre && (K != 128 || T > 4 || !rs)) return REGNN_EINVAL;
-        if (K == 128 && T <= 4 && (pre || !getenv("REGNN_NSM_AGG0_OLD"))) {  // every tile its own block
+        // K = 128 always takes agg0w: regnn_nsm_step refuses T (K + 1) > 600, so 129 T <= 600
+        // gives T <= 4 (agg0w's four register accumulators); the 256-thread agg0 is K = 64's
+        // (65 T <= 600 and T <= MT = 8: both of its NT forms are reachable)
+        if (K == 128 && T <= 4) {              // every tile its own block
             grid = (w->cap[h] + kAggRows - 1) / kAggRows;
             const size_t lds = agg0w_lds(T);
             const bool res = p->residual != 0;
@@ -2331,8 +2321,7 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
             hipLaunchKernelGGL((agg0_kernel<KK, NN, RS>), dim3(grid), dim3(kBlock), lds, stream, A); \
             REGNN_LAUNCH_CHECK();                                                              \
         } else
-        AGG0_CASE(128, 4, true) AGG0_CASE(128, MT, true) AGG0_CASE(64, 4, true)
-        AGG0_CASE(64, MT, true) AGG0_CASE(128, 4, false) AGG0_CASE(128, MT, false)
+        AGG0_CASE(64, 4, true) AGG0_CASE(64, MT, true)
         AGG0_CASE(64, 4, false) AGG0_CASE(64, MT, false)
             return REGNN_EUNSUPPORTED;
 #undef AGG0_CASE
@@ -2405,7 +2394,7 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
     }
     if (!second) return REGNN_OK;
     // 4. layer 0's backward (nb0 blocks per type: one slab row each)
-    const int nb0 = kBwdBlocks / kBwdGroups;
+    constexpr int nb0 = kBwdBlocks / kBwdGroups;
     {
         Bwd0Args B{};
         B.sizes = w->sizes; B.hop = 1; B.T = T;
@@ -2417,20 +2406,17 @@ int regnn_nsm2_step(const regnn_nsm_params* p, const regnn_nsm_work* w, hipStrea
         B.adam_step = ad ? ad->step : nullptr;
         const dim3 grid(nb0, T);
         const bool res = rs && p->residual != 0;
-#define BWD0_CASE(KK, RS, NG, RES)                                                             \
-        if (K == KK && rs == RS && kBwdGroups == NG && res == RES) {                           \
+#define BWD0_CASE(KK, RS, RES)                                                                 \
+        if (K == KK && rs == RS && res == RES) {                                               \
             static size_t done = 0;                                                            \
-            const size_t lds = bwd0_lds_floats<KK, RS, NG>(p->n_rel[0]) * sizeof(float);       \
-            if (!set_lds(reinterpret_cast<const void*>(&bwd0_kernel<KK, RS, NG, RES>), lds, &done)) \
+            const size_t lds = bwd0_lds_floats<KK, RS>(p->n_rel[0]) * sizeof(float);           \
+            if (!set_lds(reinterpret_cast<const void*>(&bwd0_kernel<KK, RS, RES>), lds, &done)) \
                 return REGNN_EUNSUPPORTED;                                                     \
-            hipLaunchKernelGGL((bwd0_kernel<KK, RS, NG, RES>), grid, dim3(kBlock * NG), lds, stream, B); \
+            hipLaunchKernelGGL((bwd0_kernel<KK, RS, RES>), grid, dim3(kBlock * kBwdGroups), lds, stream, B); \
             REGNN_LAUNCH_CHECK();                                                              \
         } else
-        BWD0_CASE(128, true, 2, false) BWD0_CASE(64, true, 2, false) BWD0_CASE(128, false, 2, false)
-        BWD0_CASE(64, false, 2, false) BWD0_CASE(128, true, 1, false) BWD0_CASE(64, true, 1, false)
-        BWD0_CASE(128, false, 1, false) BWD0_CASE(64, false, 1, false)
-        BWD0_CASE(128, true, 2, true) BWD0_CASE(64, true, 2, true)
-        BWD0_CASE(128, true, 1, true) BWD0_CASE(64, true, 1, true)
+        BWD0_CASE(128, true, false) BWD0_CASE(64, true, false) BWD0_CASE(128, false, false)
+        BWD0_CASE(64, false, false) BWD0_CASE(128, true, true) BWD0_CASE(64, true, true)
             return REGNN_EUNSUPPORTED;
 #undef BWD0_CASE
     }

@@ -65,12 +65,10 @@ class DeviceSampler:
     ntype: node type per global node (self-loop relation num_edge_types + ntype), or None."""
 
     def __init__(self, rg, sizes, batch_size, etype=None, ntype=None, num_edge_types=0,
-                 share=None, share_dedup=None):
+                 share=None):
         """share: another DeviceSampler over the same graph whose read-only tables (edge and
         node types) and dedup tables are reused (a second pipeline slot: the two never sample
-        at the same time, and their dedup stamps never coincide). share_dedup: the sampler whose
-        dedup tables to reuse instead (default: share); False: tables of its own (a slot that
-        may sample at the same time as share, on another stream)."""
+        at the same time, and their dedup stamps never coincide)."""
         dev = rg.device
         self.rg, self.device = rg, dev
         self.sizes_k = [int(k) for k in sizes]
@@ -107,13 +105,12 @@ class DeviceSampler:
         self.state = torch.zeros(8, dtype=torch.int64, device=dev)
         self.sizes = torch.zeros(16, dtype=torch.int32, device=dev)
         self.n_id = torch.zeros(caps[-1], dtype=torch.int32, device=dev)
-        dd = share if share_dedup is None else share_dedup
-        if dd:
+        if share is not None:
             # one stamp counter for both: the dedup tables need increasing stamps
-            self.g2l, self.first = dd.g2l, dd.first
-            if dd.stamp_src is None:
-                dd.stamp_src = dd.state[4:5].clone()
-            self.stamp_src = dd.stamp_src
+            self.g2l, self.first = share.g2l, share.first
+            if share.stamp_src is None:
+                share.stamp_src = share.state[4:5].clone()
+            self.stamp_src = share.stamp_src
         else:
             self.g2l = torch.zeros(n_nodes, dtype=torch.int64, device=dev)
             self.first = torch.full((n_nodes,), -1, dtype=torch.int64, device=dev)
@@ -634,11 +631,6 @@ def default_ahead(world):
 # two halves, deferred or not: the sampler's chain per batch reaches every step's edge in time,
 # so each sums launch sits beside agg0 / head), else "2". DESIGN section 4b has the runs
 SUMS_ALIGN = {"mode": os.environ.get("REGNN_NS_SUMS_ALIGN", "auto")}
-# "on": the module path sizes its GEMMs' split-K for the first batch's live rows (ops.LIVE_HINT:
-# ~6 k of the 13312-row capacity at mag-10x, split 2 with a reduce); measured at hidden 512 (3 x
-# 20 steps): 578.2 against 563.0 us per step without -- the reduce costs more than the shorter
-# k-chains save; off by default (REGNN_NS_GEMM_LIVE_HINT=on)
-GEMM_LIVE_HINT = {"mode": os.environ.get("REGNN_NS_GEMM_LIVE_HINT", "off")}
 # "on": the module path's outer hop forms layer 0's per-type input sums on the sampler's stream
 # (relation slots; NSTrainer._module_pre_sums) and layer 0 reads them; "off": layer 0 gathers the
 # sampled raw rows itself (regnn_ns_typed_agg, A/B)
@@ -649,12 +641,6 @@ MODULE_STRIDED = {"mode": os.environ.get("REGNN_NS_MODULE_STRIDED", "on")}
 # "on": FlatAdam advances its step count with a one-element add and launches regnn_adam_flat
 # without its end-of-grid ticket (ticket NULL); "off": the launch advances it behind the ticket
 ADAM_PRE_STEP = {"mode": os.environ.get("REGNN_ADAM_PRE_STEP", "on")}
-# parallel sampler lanes inside a lookahead group (REGNN_NS_SAMPLER_LANES): L streams, slot s on
-# lane s mod L with dedup tables of its own lane (L x 16 B per node of HBM). Measured (round 6):
-# L = 1 / 2 / 4 at 20 steps 110.6 / 116.0 / 133.0, at 160 steps 105.3 / 112.4 / 137.9 us per step
-# -- more sampler work at once slows the model's kernels more than the shorter sampler chain
-# saves; 1 stays
-SAMPLER_LANES = {"n": int(os.environ.get("REGNN_NS_SAMPLER_LANES", "1"))}
 # "on": the module path's last hop runs meta-only when the model's layer 0 is the typed first
 # layer (mag.REGNN.typed_first_layer_ok); "off": the full hop (A/B, tests)
 MODULE_LEAN_HOP = {"mode": os.environ.get("REGNN_NS_MODULE_LEAN", "on")}
@@ -665,10 +651,6 @@ LEAN_LAST_HOP = {"mode": "on"}
 # per-type input sums (regnn_ns_hop_typed_sums) on the sampler's stream, ahead of the model, and
 # agg0 reads them (regnn_nsm_work.pre_sums); "off": agg0 gathers the raw rows itself (A/B, tests)
 PRE_SUMS = {"mode": os.environ.get("REGNN_NS_PRE_SUMS", "on")}
-# capture order of a lookahead group's launches: "model" (every model step, then every sampler
-# batch) or "interleave" (model step i, then sampler batch i): the same dependency edges; measured
-# (round 6, 20-step runs) within run-to-run spread of each other, so "model" stays
-GROUP_ORDER = {"mode": os.environ.get("REGNN_NS_GROUP_ORDER", "model")}
 
 
 # "on": where the graph's node ids are grouped by type (type_layout below), the sampler's sums
@@ -1311,19 +1293,10 @@ class NSTrainer:
             # 573 MB per [cap_src, 512] tensor at 8 heads x 64, batch 512, fan-out [25, 20])
             self.ahead = max(1, int(default_ahead(self.world) if self.fused is not None
                                     else 1 if self._gat_blocks else MODULE_AHEAD["n"]))
-        # parallel sampler lanes (lookahead groups): slot s samples on lane s mod L with that
-        # lane's own dedup tables, so L batches of a group sample at the same time on L streams
-        self.lanes = (max(1, int(SAMPLER_LANES["n"])) if self.pipelined and self.fused is not None
-                      and self.ahead > 1 else 1)
-        if self.lanes > 1 and (2 * self.ahead) % self.lanes:
-            raise ValueError(f"{self.lanes} sampler lanes must divide the {2 * self.ahead} slots")
         if self.pipelined:
             for j in range(1, 2 * self.ahead):
-                lane = j % self.lanes
                 self.slots.append(DeviceSampler(
-                    rg, sizes, batch_size, num_edge_types=num_edge_types, share=self.slots[0],
-                    share_dedup=(False if j == lane else self.slots[lane]) if self.lanes > 1
-                    else None))
+                    rg, sizes, batch_size, num_edge_types=num_edge_types, share=self.slots[0]))
             if self.fused is not None:
                 self.fused_slots = [self.fused] + [
                     FusedStep(model, s, x_dict, node_type, local_node_idx, self.y_flat, self.loss)
@@ -1334,8 +1307,6 @@ class NSTrainer:
             # the sampler's stream; REGNN_NS_SIDE_PRIORITY (-1: high) for A/B runs
             self._side = torch.cuda.Stream(device=dev,
                                            priority=int(os.environ.get("REGNN_NS_SIDE_PRIORITY", "0")))
-            self._sides = [self._side] + [torch.cuda.Stream(device=dev)
-                                          for _ in range(self.lanes - 1)]
         # one rank, FlatAdam, two-layer step: the optimizer runs inside the step's last launch
         # (no all-reduce sits between the backward and the update)
         self.adam_fused = (self.fused is not None and self.fused.two_layer and self.world == 1
@@ -1542,8 +1513,8 @@ class NSTrainer:
         trained last) on the second one; one fork before, one join after."""
         cs = torch.cuda.current_stream(self.device)
         G, n = self.ahead, len(self.slots)
-        for sd in self._sides:
-            sd.wait_stream(cs)
+        sd = self._side
+        sd.wait_stream(cs)
         # "on": every step; an integer N: the sums of batches i = N, 2N, .. only (each event
         # record is a marker on the model's queue: ~4 us of queue idle between finalize and the
         # next agg0, measured in a kernel trace); "off": never
@@ -1571,27 +1542,20 @@ class NSTrainer:
 
         def sampler(i):
             slot = (start + G + i) % n
-            sd = self._sides[slot % self.lanes]
             with torch.cuda.stream(sd):
                 # batch i's outer-hop sums (the sampler's one heavy launch) wait for the end of
                 # model step i - 1, so they run beside step i's agg0 / head (which they slow
                 # little) instead of its gather / bwd0 / finalize (2-4x slower beside them)
-                wait = ((lambda e=ends[i - 1], sd=sd: sd.wait_event(e))
+                wait = ((lambda e=ends[i - 1]: sd.wait_event(e))
                         if align and i and (i - 1) in ends else None)
                 self._sample(slot, before_sums=wait)
 
-        if GROUP_ORDER["mode"] == "interleave":
-            for i in range(m):
-                model(i)
-                sampler(i)
-        else:
-            # the model's launches first (captured first: the graph runs them on the launch queue)
-            for i in range(m):
-                model(i)
-            for i in range(m):
-                sampler(i)
-        for sd in self._sides:
-            cs.wait_stream(sd)
+        # the model's launches first (captured first: the graph runs them on the launch queue)
+        for i in range(m):
+            model(i)
+        for i in range(m):
+            sampler(i)
+        cs.wait_stream(sd)
 
     def _group_sizes(self):
         return group_sizes(self.ahead)
@@ -1629,17 +1593,6 @@ class NSTrainer:
 
     def _module_step(self, s):
         """the mag.REGNN autograd forward / nll / backward on sampler slot s's batch."""
-        if (self._blocks_ok and GEMM_LIVE_HINT["mode"] == "on" and
-                not getattr(self, "_live_hinted", False) and
-                not torch.cuda.is_current_stream_capturing()):
-            # the GEMMs' split-K sized for the live rows of a typical block (one host read of
-            # the first batch's sizes, eager, before any capture): ops.LIVE_HINT
-            from . import ops
-            torch.cuda.current_stream(self.device).synchronize()
-            sz = s.sizes.cpu().tolist()
-            for h in range(1, len(s.caps) - 1):
-                ops.set_live_hint(s.caps[h], sz[h])
-            self._live_hinted = True
         # the bucket zeroed once: every step overwrites each gradient the forward produces, and
         # a parameter the forward never reads (allow_unused) keeps the zeros (no fill per step)
         if not getattr(self, "_flat_zeroed", False):

@@ -150,12 +150,14 @@ def test_mm_live_rows_bitwise(live, hint, monkeypatch):
     """ops.mm with a live-row count (the capacity-sized block's rows past it are zero): the
     forward and both gradients bitwise those of the full GEMMs on the same zero-padded operands
     (the skipped products are exact zeros), the output's dead rows equal to c's. hint: the
-    trainer's typical live rows for this capacity (ops.LIVE_HINT): the 13312-row products split
-    K in two (the dead row tiles write no partial, the reduce skips their rows) with and without
-    the live count alike; against fp64 at 1e-5 too."""
+    split-K factor sized for that many rows in place of the 13312-row capacity: the 13312-row
+    products split K in two (the dead row tiles write no partial, the reduce skips their rows)
+    with and without the live count alike; against fp64 at 1e-5 too."""
     from regnn_hip import ops
-    monkeypatch.setattr(ops, "LIVE_HINT", {} if hint is None else {13312: hint})
     if hint is not None:
+        splits = ops._gemm_splits
+        monkeypatch.setattr(ops, "_gemm_splits",
+                            lambda M, N, K: splits(hint if M == 13312 else M, N, K))
         assert ops._gemm_splits(13312, 512, 516) == 2
     g = torch.Generator(device=DEV).manual_seed(11)
     M, K, N = 13312, 516, 512

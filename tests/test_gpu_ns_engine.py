@@ -840,16 +840,13 @@ def test_transposed_index_after_csr_batches():
             assert sorted(ce[cp[u]:cp[u + 1]].tolist()) == sorted(want[u]), (it, strided, u)
 
 
-@pytest.mark.parametrize("half_waves", ["0", "1"])
-def test_strided_blocks_match_csr(monkeypatch, half_waves):
+def test_strided_blocks_match_csr(monkeypatch):
     """regnn_ns_hop strided (the fused engine's fixed-stride blocks: sampling and placement in one
     launch) against the CSR layout on the same batches: the same n_id, sizes, per-row edges
     (local source, relation, CSR position, target row; the meta-only hop's source type / table
     row), 1/in-counts and transposed index; and the two-layer fused step's loss and gradients
-    bitwise equal over both layouts. half_waves "1": the strided sampler with two targets per
-    wave (fan-outs 9 and 7 fit 32 lanes)."""
+    bitwise equal over both layouts."""
     from regnn_hip import ns
-    monkeypatch.setenv("REGNN_NS_HALF_WAVES", half_waves)
     d = _mag(0.003, seed=10, F=128, hidden=64, classes=19, dropout=0.5)
     trs, models = [], []
     for mode in ("off", "on"):

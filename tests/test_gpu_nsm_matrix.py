@@ -141,21 +141,17 @@ def test_nsm_step_no_labelled_target():
     assert out["ref"]["nvalid"] == 0 and out["loss"] == 0.0
 
 
-@pytest.mark.parametrize("mode", ["default", "strided_off", "lean_off", "pre_sums_off",
-                                  "agg0_old"])
+@pytest.mark.parametrize("mode", ["default", "strided_off", "lean_off", "pre_sums_off"])
 def test_nsm_step_modes(monkeypatch, mode):
     """the two-layer step's sampler layouts and agg0 forms on one batch: CSR blocks, the full
-    last hop, agg0's own gather (each turns the sampler's input sums off), and the 256-thread
-    agg0 (REGNN_NSM_AGG0_OLD, read where agg0 gathers itself)."""
+    last hop and agg0's own gather (each turns the sampler's input sums off)."""
     from regnn_hip import ns
     if mode == "strided_off":
         monkeypatch.setitem(ns.STRIDED, "mode", "off")
     if mode == "lean_off":
         monkeypatch.setitem(ns.LEAN_LAST_HOP, "mode", "off")
-    if mode in ("pre_sums_off", "agg0_old"):
+    if mode == "pre_sums_off":
         monkeypatch.setitem(ns.PRE_SUMS, "mode", "off")
-    if mode == "agg0_old":
-        monkeypatch.setenv("REGNN_NSM_AGG0_OLD", "1")
     _run("10-t4-k128-modes", strided=mode != "strided_off", lean=mode != "lean_off",
          pre_sums=int(mode == "default"))
 
