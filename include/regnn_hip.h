@@ -1372,6 +1372,44 @@ int regnn_wide_ln_bwd(int64_t n, int32_t H, const float* gy, const float* a, con
                       const int64_t* state, int32_t layer, float p_drop, float* gx, float* gres,
                       float* slab, const int32_t* live, hipStream_t stream);
 
+/* ---- The same epilogue with BatchNorm1d in training mode (mag/regnn_layers.py:64-65,134-135
+ * with use_norm 'bn'), over the LIVE rows of a capacity-sized sampled block -----------------------
+ * Every H % 4 == 0 in [4, 1024] (other widths: REGNN_EUNSUPPORTED); 16-byte aligned rows.
+ * live: a device int32 count (NULL: n), read on the device by every launch (all grids are sized
+ * from n: a captured graph replays with whatever count the sampler wrote); L = min(n, *live).
+ * Forward (3 launches): a = rs[v] x[v] + bias (+ res[v]) for v < L; the column mean and biased
+ * variance over those L rows; y = dropout(relu(gamma (a - mean) rsqrt(var + eps) + beta)) for
+ * v < L and y = 0 for L <= v < n; stats [2][H] = (mean, rstd). a and stats' mean are work buffers
+ * for the backward and are stored centred on row 0 (a[v] - a[0] formed in fp64 and rounded once,
+ * mean - a[0]): a column mean far from 0 then costs no precision. Dropout: the mask spec of
+ * regnn_wide_ln_fwd (the same (state, layer) draws the same mask). The running buffers:
+ *   running_mean = (1 - momentum) running_mean + momentum mean
+ *   running_var  = (1 - momentum) running_var  + momentum var L / (L - 1)
+ *   num_batches_tracked (int64, may be NULL) += 1
+ * L < 2 (torch raises there; a device count cannot): the rows are normalised with var = 0 and
+ * running_mean, running_var and num_batches_tracked are left untouched.
+ * The statistics use no atomics and give the same bits on every run: per-block (count, mean,
+ * M2 about the block's own mean) in slab [regnn_wide_bn_slab_rows(n, H)][3 H], merged in block
+ * order with Chan et al.'s update (never E[a^2] - mean^2).
+ * Backward (3 launches) from gy, a and stats: gy' = gy mask [gamma xhat + beta > 0];
+ * sums [2][H] = (g_beta = sum gy', g_gamma = sum gy' xhat) over the L rows (slab partials summed
+ * in block order); ga = gamma rstd (gy' - g_beta / L - xhat g_gamma / L); gx = rs ga, gres = ga
+ * (optional) for v < L, zeros for L <= v < n. The conv bias's gradient, sum_v ga, is exactly 0
+ * under batch norm and is not computed. act: 1 as above; 0: the norm alone, y = gamma xhat +
+ * beta without relu or dropout (p_drop must be 0), for a caller that applies them itself. */
+int64_t regnn_wide_bn_slab_rows(int64_t n, int32_t H);
+int regnn_wide_bn_fwd(int64_t n, int32_t H, const float* x, const float* rs, const float* bias,
+                      const float* res, const float* gamma, const float* beta,
+                      const int64_t* state, int32_t layer, float p_drop, float* a, float* stats,
+                      float* y, float* slab, const int32_t* live, float* running_mean,
+                      float* running_var, int64_t* num_batches_tracked, float eps, float momentum,
+                      int32_t act, hipStream_t stream);
+int regnn_wide_bn_bwd(int64_t n, int32_t H, const float* gy, const float* a, const float* stats,
+                      const float* rs, const float* gamma, const float* beta,
+                      const int64_t* state, int32_t layer, float p_drop, float* gx, float* gres,
+                      float* slab, float* sums, const int32_t* live, int32_t act,
+                      hipStream_t stream);
+
 /* ---- Per-node-type input rows of the ogbn-mag path (mag/regnn_ns.py:300-326, group_input) ----
  * The reference builds the batch's input matrix with one boolean mask per node type (a host
  * sync each) and, for feats_type != 2, runs each type's Linear over its masked subset. Node i of

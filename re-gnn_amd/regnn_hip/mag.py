@@ -84,9 +84,16 @@ class REGCNConv(torch.nn.Module):
             agg = ops.ns_spmm(edge_index, x_src, tab)
             if self.residual:
                 agg = agg + x_target
-            out = ops.mm(agg, self.weight, self.bias)
-            if self.use_norm in ('bn', 'ln'):
-                out = self.norm(out)                                             # :134-135
+            if self._bn_live(edge_index):
+                # a capacity-sized block: the batch statistics over its live rows only, zeros
+                # past them (ops.wide_bn_act without its relu / dropout; torch's BatchNorm1d
+                # would count the padded rows)
+                out = ops.wide_bn_act(ops.mm(agg, self.weight), self.bias, self.norm,
+                                      live=edge_index.live_rows, act=False)
+            else:
+                out = ops.mm(agg, self.weight, self.bias)
+                if self.use_norm in ('bn', 'ln'):
+                    out = self.norm(out)                                         # :134-135
             if return_weights:
                 return out, self._edge_weights(edge_index, edge_type, target_node_type, tab,
                                                x_target.shape[0]), tab
@@ -109,14 +116,24 @@ class REGCNConv(torch.nn.Module):
 
     def forward_act(self, x_src, x_target, blk, p, state, layer, tab=None):
         """forward() on a device-sampled block followed by the model's relu and dropout, the
-        bias / LayerNorm / relu / dropout as one launch (ops.wide_ln_act). tab: this layer's
-        relation table when the caller formed it (ops.rel_tabs)."""
+        bias / LayerNorm / relu / dropout as one launch (ops.wide_ln_act); use_norm 'bn' in
+        training mode: ops.wide_bn_act over the block's live rows. tab: this layer's relation
+        table when the caller formed it (ops.rel_tabs)."""
         if tab is None:
             tab = ops.rel_tab(self.relation_weight, self.scaling_factor)        # :110-111
         agg = ops.ns_spmm(blk, x_src, tab)
         if self.residual:
             agg = agg + x_target
+        if self._bn_live(blk):
+            return ops.wide_bn_act(ops.mm(agg, self.weight), self.bias, self.norm, p, state,
+                                   layer, live=blk.live_rows)
         return ops.wide_ln_act(ops.mm(agg, self.weight), self.bias, self.norm, p, state, layer)
+
+    def _bn_live(self, blk):
+        """True where this conv's BatchNorm must take its statistics over the live rows of a
+        capacity-sized block (training mode, the block carries its live count)."""
+        return (self.use_norm == 'bn' and self.norm.training and
+                getattr(blk, "live_rows", None) is not None)
 
     def _edge_weights(self, edge_index, edge_type, target_node_type, tab, n_dst):
         """ew of mag/regnn_layers.py:110-126 per edge in the reference's order (sampled edges,
@@ -518,7 +535,16 @@ class REGNN(torch.nn.Module):
 
     def _wide_epi(self, blk):
         """(dropout p, state) when the device-block layers may run the fused wide epilogue
-        (ops.wide_ln_act), else None."""
+        (ops.wide_ln_act), else None. use_norm 'bn' in training mode on a block that carries its
+        live count: ops.wide_bn_act at every width (its statistics must leave the block's padded
+        rows out, so neither the knob nor a lower bound on the width applies)."""
+        if (self.model == 'regcn' and self.convs and
+                all(c.use_norm == 'bn' and c._bn_live(blk) for c in self.convs)):
+            p = float(self.dropout) if self.training else 0.0
+            state = getattr(blk, "state", None)
+            # (dropout without the sampler state: the convs still normalise over the live rows,
+            # REGCNConv.forward, and torch draws the mask)
+            return None if p > 0 and state is None else (p, state)
         if (WIDE_EPI["mode"] == "off" or self.model != 'regcn' or self.hidden_dim < 128 or
                 self.hidden_dim not in ops.WIDE_LN_WIDTHS or
                 any(c.use_norm != 'ln' for c in self.convs)):
@@ -583,6 +609,13 @@ class REGNN(torch.nn.Module):
         if conv.residual:                                                       # :104,131-132
             x_t = self.group_input(x_dict, node_type, local_node_idx, n_id[:n])
             res = ops.mm(x_t, conv.weight)
+        if conv._bn_live(blk):
+            # BatchNorm over the block's live rows, zeros past them (with the residual too: the
+            # statistics depend on the count); with `epi` the relu and dropout ride along
+            act = epi is not None
+            return ops.wide_bn_act(agg, conv.bias, conv.norm, epi[0] if act else 0.0,
+                                   epi[1] if act else None, 0, rs=blk.inv[:n], res=res,
+                                   live=blk.live_rows, act=act), act
         if epi is not None and ops.wide_ln_ok(agg, conv.norm, conv.bias):
             # mean + bias + residual, LayerNorm, relu, dropout in one launch (:341-343)
             # (only the block's live rows: without residuals every consumer of layer 0's rows is
@@ -643,7 +676,9 @@ class REGNN(torch.nn.Module):
             blk = edge_index if getattr(edge_index, "is_ns_block", False) else \
                 getattr(adj, "block", None)
             if (blk is not None and getattr(blk, "is_ns_block", False) and epi is not None and
-                    self.self_loop_type == 2 and ops.wide_ln_ok(x, self.convs[i].norm, self.convs[i].bias)):
+                    self.self_loop_type == 2 and
+                    (self.convs[i]._bn_live(blk) or
+                     ops.wide_ln_ok(x, self.convs[i].norm, self.convs[i].bias))):
                 ep = self._wide_epi(blk) or epi
                 x = self.convs[i].forward_act(x, x_target, blk, ep[0], ep[1], i,
                                               tab=None if tabs is None else tabs[i])

@@ -1207,6 +1207,20 @@ class NSTrainer:
             # builds them beside the hops (_sample); the backwards then use no float atomics
             from . import ops as _ops
             self._gat_src_gather = _ops.ns_gat_src_mode() == "gather"
+        # use_norm 'bn' on the capacity-sized blocks: the batch statistics are taken over the
+        # block's live rows by ops.wide_bn_act, never by torch's BatchNorm1d over the padded rows;
+        # where that operator does not cover a conv the trainer refuses (no silent fall-back)
+        if self._blocks_ok and not self._gat_blocks:
+            from . import ops as _ops
+            for i, c in enumerate(getattr(model, "convs", [])):
+                if getattr(c, "use_norm", None) != "bn":
+                    continue
+                bad = _ops.wide_bn_module_why_not(c.norm, int(c.out_channels), c.bias)
+                if bad is not None:
+                    raise ValueError(
+                        f"use_norm 'bn': conv {i} cannot take its batch statistics over the "
+                        f"block's live rows (ops.wide_bn_act): {bad}; torch's BatchNorm1d would "
+                        "include the capacity-sized block's padded rows")
         self.params = [p for p in model.parameters() if p.requires_grad]
         # every parameter starts on a 16-byte boundary of the flat buckets (the fused step's
         # finalize sums and steps 4 aligned elements per thread); the pad elements stay zero.
@@ -1728,16 +1742,20 @@ class NSTrainer:
 
     def _train_state(self):
         """parameters and optimizer state, for capture() to undo its warm-up steps."""
+        # (and the model's buffers: BatchNorm's running statistics move with every step)
+        bufs = [b.detach().clone() for b in self.model.buffers()]
         if isinstance(self.opt, FlatAdam):
             o = self.opt
-            return [t.clone() for t in (o.p, o.m, o.v, o.step_count)], None
+            return [t.clone() for t in (o.p, o.m, o.v, o.step_count)], None, bufs
         st = {id(p): {k: v.clone() for k, v in s.items() if torch.is_tensor(v)}
               for p, s in self.opt.state.items()}
-        return [p.detach().clone() for p in self.params], st
+        return [p.detach().clone() for p in self.params], st, bufs
 
     def _restore_train_state(self, saved):
-        flat, st = saved
+        flat, st, bufs = saved
         with torch.no_grad():
+            for b, src in zip(self.model.buffers(), bufs):
+                b.copy_(src)
             if st is None:
                 o = self.opt
                 for dst, src in zip((o.p, o.m, o.v, o.step_count), flat):

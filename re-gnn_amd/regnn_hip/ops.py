@@ -2583,3 +2583,116 @@ def wide_ln_act(x, bias, ln, p=0.0, state=None, layer=0, rs=None, res=None, live
         live = None
     return _WideLn.apply(x, bias, res, ln.weight, ln.bias,
                          rs, state if p > 0 else None, layer, float(p), live)
+
+
+# ---------------------------------------------------------------------------------------------
+# the same epilogue with BatchNorm1d (training mode) over a capacity-sized block's LIVE rows:
+# rs x + bias (+ res) -> BatchNorm over rows < live -> relu -> dropout; zeros past the live rows
+# ---------------------------------------------------------------------------------------------
+class _WideBn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bias, res, gamma, beta, rs, state, layer, p, live, rmean, rvar, nbt, eps,
+                mom, act):
+        n, H = x.shape
+        a = torch.empty_like(x)
+        y = torch.empty_like(x)
+        stats = torch.empty(2, H, dtype=torch.float32, device=x.device)
+        rows = int(L._so.regnn_wide_bn_slab_rows(n, H))
+        slab = torch.empty(rows, 3 * H, dtype=torch.float32, device=x.device)
+        L.call("regnn_wide_bn_fwd", n, H, L.ptr(x), L.ptr(rs), L.ptr(bias), L.ptr(res),
+               L.ptr(gamma), L.ptr(beta), L.ptr(state), int(layer), float(p), L.ptr(a),
+               L.ptr(stats), L.ptr(y), L.ptr(slab), L.ptr(live), L.ptr(rmean), L.ptr(rvar),
+               L.ptr(nbt), float(eps), float(mom), int(act), L.stream())
+        ctx.save_for_backward(a, stats, rs, gamma, beta, state, live)
+        ctx.layer, ctx.p, ctx.act = int(layer), float(p), int(act)
+        ctx.has_res, ctx.has_bias = res is not None, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        a, stats, rs, gamma, beta, state, live = ctx.saved_tensors
+        n, H = a.shape
+        gy = gy.contiguous()
+        if gy.data_ptr() % 16:                 # the kernel's float4 rows need 16-byte alignment
+            gy = gy.clone()
+        gx = torch.empty_like(a)
+        gres = torch.empty_like(a) if ctx.has_res and ctx.needs_input_grad[2] else None
+        rows = int(L._so.regnn_wide_bn_slab_rows(n, H))
+        slab = torch.empty(rows, 3 * H, dtype=torch.float32, device=a.device)
+        sums = torch.empty(2, H, dtype=torch.float32, device=a.device)
+        L.call("regnn_wide_bn_bwd", n, H, L.ptr(gy), L.ptr(a), L.ptr(stats), L.ptr(rs),
+               L.ptr(gamma), L.ptr(beta), L.ptr(state), ctx.layer, ctx.p, L.ptr(gx), L.ptr(gres),
+               L.ptr(slab), L.ptr(sums), L.ptr(live), ctx.act, L.stream())
+        # the conv bias's gradient is sum_v ga, exactly 0 under batch norm: zeros, no reduction
+        g_bias = torch.zeros(H, dtype=a.dtype, device=a.device) \
+            if ctx.has_bias and ctx.needs_input_grad[1] else None
+        return (gx, g_bias, gres, sums[1], sums[0]) + (None,) * 11
+
+
+def wide_bn_why_not(x, bn, bias=None):
+    """why ops.wide_bn_act cannot take (x, bn, bias), or None when it can."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return "the rows must be a 2-D fp32 device tensor"
+    H = x.shape[1]
+    if H % 4 or not 4 <= H <= 1024:
+        return f"width {H}: regnn_wide_bn_fwd takes H % 4 == 0, 4 <= H <= 1024"
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        return "the rows must be contiguous and 16-byte aligned"
+    return wide_bn_module_why_not(bn, H, bias)
+
+
+def wide_bn_module_why_not(bn, H, bias=None):
+    """the part of wide_bn_why_not that depends on the module and the width alone."""
+    if H % 4 or not 4 <= H <= 1024:
+        return f"width {H}: regnn_wide_bn_fwd takes H % 4 == 0, 4 <= H <= 1024"
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        return "the norm is not a BatchNorm1d"
+    if bn.num_features != H:
+        return f"BatchNorm1d has {bn.num_features} features, the rows {H}"
+    if bn.momentum is None:
+        return "BatchNorm1d(momentum=None) (a cumulative average) is not covered"
+    if not bn.affine:
+        return "BatchNorm1d(affine=False) is not covered"
+    if not bn.track_running_stats or bn.running_mean is None:
+        return "BatchNorm1d(track_running_stats=False) is not covered"
+    ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return "BatchNorm1d's parameters and buffers must be fp32 device tensors"
+    if not _wide_operands_ok(bias, *ts):
+        return "the bias and BatchNorm1d's weight / bias must be contiguous and 16-byte aligned"
+    return None
+
+
+def wide_bn_ok(x, bn, bias=None):
+    return wide_bn_why_not(x, bn, bias) is None
+
+
+def wide_bn_act(x, bias, bn, p=0.0, state=None, layer=0, rs=None, res=None, live=None, act=True):
+    """dropout(relu(BatchNorm1d(rs * x + bias + res))) in training mode (regnn_wide_bn_fwd / _bwd:
+    three launches each way), the batch statistics over the rows below `live` only -- a
+    one-element int32 device count (None: every row), read on the device. Rows past it come out
+    zero, forward and backward, with `res` as well. bn.running_mean / running_var /
+    num_batches_tracked are updated in place (left untouched for fewer than 2 live rows, where the
+    rows are normalised with variance 0). The dropout mask is wide_ln_act's for the same
+    (state, layer). Training mode only: in eval mode BatchNorm1d is a per-row affine map and
+    torch's composition is already right. act=False: the norm alone, no relu and no dropout
+    (p must be 0), for a caller that applies them itself."""
+    if not bn.training:
+        raise ValueError("wide_bn_act covers training mode (batch statistics); in eval mode use "
+                         "the module")
+    why = wide_bn_why_not(x, bn, bias)
+    if why is not None:
+        raise ValueError(f"wide_bn_act: {why} (check wide_bn_ok first)")
+    if p > 0 and not act:
+        raise ValueError("wide_bn_act: act=False takes no dropout")
+    if p > 0 and state is None:
+        raise ValueError("wide_bn_act: dropout needs the sampler state (its mask key)")
+    if res is not None:
+        res = res.contiguous()
+        if res.data_ptr() % 16:
+            res = res.clone()
+    if live is not None and not (live.is_cuda and live.dtype == torch.int32 and live.numel() == 1):
+        raise ValueError("wide_bn_act: live must be a one-element int32 device tensor")
+    return _WideBn.apply(x, bias, res, bn.weight, bn.bias, rs, state if p > 0 else None, layer,
+                         float(p), live, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                         float(bn.eps), float(bn.momentum), bool(act))
