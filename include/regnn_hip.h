@@ -1122,6 +1122,33 @@ int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t
                            const float* gS, const float* gw, int64_t ld_s, int64_t ld_w,
                            float* slab, int32_t n_rel, int32_t slab_rows, hipStream_t stream);
 
+/* regnn_ns_typed_agg / _bwd with one input width per node type (feats_type 5 of
+ * mag/regnn_ns.py:185-194: paper rows cat[x, embedding] 256 wide, the other types 128): K_t is a
+ * host array of n_types widths, each in {64, 128, 256}; tables[t] is fp32 [*, K_t[t]], 16-byte
+ * aligned. Row v of S is [S_0 (K_0) | S_1 (K_1) | .. | S_{T-1}], S_t at column c_t = sum_{u<t} K_u
+ * (ld_s >= sum K_t, a multiple of 4, S 16-byte aligned); wsum as above, so with wsum = S + sum K_t
+ * and ld_s = ld_w = sum K_t + Tp the row is the operand [S | w | 0] of one GEMM against
+ * [W_0^T; ..; W_{T-1}^T; b_0; ..; 0] W_conv. e_off / local are table ROWS (scaled by K_t here).
+ * Every (row, type, column) sum is formed by fmaf in CSR entry order as regnn_ns_typed_agg forms
+ * it: with all K_t equal to 64 or 128, S and wsum hold that entry's bits. The backward's dot runs
+ * over max K_t / 4 lanes (bitwise reproducible, no float atomics; not the equal-width entry's
+ * bits). A K_t outside {64, 128, 256}: REGNN_EUNSUPPORTED; NULL K_t or table, a misaligned table /
+ * S / gS, n_types outside 1..8, ld_s < sum K_t or not a multiple of 4, n_rel > 256: REGNN_EINVAL,
+ * all before any launch. Added without an ABI bump (the version stays 51): new symbols only. */
+int regnn_ns_typed_agg_kt(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                          const float* rel_table, const int32_t* n_id, const int32_t* ntype,
+                          const int64_t* local, const int32_t* e_type, const int64_t* e_off,
+                          const float* const* tables, int32_t n_types, const int32_t* K_t,
+                          int64_t n_rows, float* S, float* wsum, int64_t ld_s, int64_t ld_w,
+                          hipStream_t stream);
+int regnn_ns_typed_agg_kt_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                              const int32_t* n_id, const int32_t* ntype, const int64_t* local,
+                              const int32_t* e_type, const int64_t* e_off,
+                              const float* const* tables, int32_t n_types, const int32_t* K_t,
+                              int64_t n_rows, const float* gS, const float* gw, int64_t ld_s,
+                              int64_t ld_w, float* slab, int32_t n_rel, int32_t slab_rows,
+                              hipStream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------
  * Fused NS model step: the REGNN of mag/regnn_ns.py:216-346 (model 'regcn', self_loop_type 2,
@@ -1451,6 +1478,37 @@ int regnn_typed_linear_wgrad(const int64_t* order, const int64_t* src, const int
                              int64_t n, int32_t T, const float* const* tab, const int32_t* wgroup,
                              int32_t G, int32_t K, int32_t O, const float* gY, float* slab,
                              float* const* gW, float* const* gb, hipStream_t stream);
+
+/* A canonical order for a block's transposed index (regnn_ns_hop csc_ptr / csc_ent): the builds
+ * place a source's entries in the order an integer atomic hands out, which differs from run to
+ * run; regnn_ns_spmm_bwd_csc sums floats in entry order, so its gradients then differ in their
+ * last bits between runs. csc_sorted (another buffer of cap_e ints) receives every segment of the
+ * n = sizes[size_idx] live sources (n <= cap_src) sorted by entry value: the same index, the same
+ * order on every run. Segments outside [0, cap_e] are skipped. One launch, no host size. Added
+ * without an ABI bump (the version stays 51): a new symbol only. */
+int regnn_ns_csc_sort(const int32_t* sizes, int32_t size_idx, const int32_t* csc_ptr,
+                      const int32_t* csc_ent, int32_t* csc_sorted, int32_t cap_src,
+                      int32_t cap_e, hipStream_t stream);
+
+/* regnn_typed_linear_fwd / _wgrad with one input width per node type: K_t a host array of T widths, each in
+ * {64, 128, 256} (else REGNN_EUNSUPPORTED), tab[t] [*, K_t[t]], W[t] [O, K_t[t]]. One launch per
+ * distinct width over the same chunk walk (a block whose chunk's type has another width returns
+ * at once): every row gets what regnn_typed_linear_fwd gives it at its own width, bit for bit.
+ * wgrad: gW[g] [O, K of g's types]; a weight group may join types of one width only
+ * (REGNN_EINVAL otherwise, and for a group no type maps to). Its slab holds
+ * regnn_typed_slab_floats(n, T, max K_t, O) floats (no _kt companion: call it with the widest
+ * K_t): every chunk takes O (max K_t + 1) floats, of which a chunk of type t fills
+ * [O][K_t] | [O]; reduced in fixed chunk order (deterministic, no atomics). Added without an ABI
+ * bump (the version stays 51): new symbols only. */
+int regnn_typed_linear_fwd_kt(const int64_t* order, const int64_t* src, const int32_t* type_off,
+                              int64_t n, int32_t T, const float* const* tab,
+                              const float* const* W, const float* const* b, const int32_t* K_t,
+                              int32_t O, float* Y, hipStream_t stream);
+int regnn_typed_linear_wgrad_kt(const int64_t* order, const int64_t* src, const int32_t* type_off,
+                                int64_t n, int32_t T, const float* const* tab,
+                                const int32_t* wgroup, int32_t G, const int32_t* K_t, int32_t O,
+                                const float* gY, float* slab, float* const* gW, float* const* gb,
+                                hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -202,6 +202,172 @@ typed_agg_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* 
     }
 }
 
+// ---- one input width per node type (feats_type 5: paper rows 256 wide, the others 128) -------
+// The same sums over tables of widths K_t in {64, 128, 256}: S row v is [S_0 (K_0) | S_1 (K_1) |
+// ..], S_t at column c_t = sum_{u < t} K_u. LPR = KM / 4 lanes per row for the widest table KM;
+// an edge of type t is read by the group's first K_t / 4 lanes (one float4 each), the others sit
+// the load out and add zeros to an accumulator that is never stored. Lane l keeps columns
+// 4 l .. 4 l + 3 of every S_t, summed by fmaf in entry order as typed_agg_kernel does: with all
+// K_t = KM the two kernels give the same bits.
+struct Widths {
+    int kq[kMT];               // K_t / 4: float4 per row of table t
+    int cq[kMT];               // c_t / 4: S_t's first float4 in an output row
+};
+
+template <int N>
+__device__ __forceinline__ int pick_kq(const Widths& w, int i) {
+    int r = w.kq[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k)
+        if (i == k) r = w.kq[k];
+    return r;
+}
+
+template <int KM, int NT>
+__global__ void __launch_bounds__(kBlock)
+typed_agg_kt_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
+                    const float* __restrict__ tab, Tabs xt, Widths W, int T, int64_t n_rows,
+                    float* __restrict__ S, float* __restrict__ wsum, int64_t lds, int64_t ldw) {
+    constexpr int LPR = KM / 4;
+    constexpr int RPW = 64 / LPR;
+    constexpr int UN = 4;
+    const int lane = threadIdx.x & 63, l = lane % LPR, gl = lane - l;
+    const int64_t rows_per_block = int64_t(kBlock / 64) * RPW;
+    for (int64_t v0 = int64_t(blockIdx.x) * rows_per_block; v0 < n_rows;
+         v0 += int64_t(gridDim.x) * rows_per_block) {
+        const int64_t v = v0 + (threadIdx.x >> 6) * RPW + lane / LPR;
+        if (v >= n_rows) continue;
+        float4 acc[NT];
+        float ws[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            ws[k] = 0.f;
+        }
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        for (int c = e0; c < e1; c += LPR) {
+            int mt, mr;
+            int64_t mrow;
+            float mw;
+            edge_meta<LPR>(E, rel, tab, c + l, e1, mt, mrow, mw, mr);
+            const int m = min(LPR, e1 - c);
+            for (int j = 0; j < m; j += UN) {
+                float4 x[UN];
+                int tt[UN];
+                float ww[UN];
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int src = gl + min(j + u, m - 1);
+                    tt[u] = __shfl(mt, src, 64);
+                    const int64_t rw = __shfl(mrow, src, 64);
+                    ww[u] = j + u < m ? __shfl(mw, src, 64) : 0.f;
+                    const int kq = pick_kq<NT>(W, tt[u]);
+                    x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (l < kq)
+                        x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
+                }
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+#pragma unroll
+                    for (int k = 0; k < NT; ++k) {
+                        if (tt[u] == k) {
+                            acc[k].x = fmaf(ww[u], x[u].x, acc[k].x);
+                            acc[k].y = fmaf(ww[u], x[u].y, acc[k].y);
+                            acc[k].z = fmaf(ww[u], x[u].z, acc[k].z);
+                            acc[k].w = fmaf(ww[u], x[u].w, acc[k].w);
+                            ws[k] += ww[u];
+                        }
+                    }
+                }
+            }
+        }
+        float4* srow = reinterpret_cast<float4*>(S + v * lds);
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+            if (k < T && l < W.kq[k]) srow[W.cq[k] + l] = acc[k];
+        if (l < T) {
+            float s = ws[0];
+#pragma unroll
+            for (int k = 1; k < NT; ++k)
+                if (l == k) s = ws[k];
+            wsum[v * ldw + l] = s;
+        }
+    }
+}
+
+// its relation-table gradient, in typed_agg_bwd_kernel's slab form (per-group LDS bins, no float
+// atomics); the dot's butterfly runs over KM / 4 lanes, the lanes past K_t / 4 adding zeros
+template <int KM, int NT>
+__global__ void __launch_bounds__(kBlock)
+typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
+                        const uint8_t* __restrict__ rel, Tabs xt, Widths W, int T, int64_t n_rows,
+                        const float* __restrict__ gS, const float* __restrict__ gw,
+                        float* __restrict__ slab, int n_rel, int64_t lds, int64_t ldw) {
+    constexpr int LPR = KM / 4;
+    constexpr int RPW = 64 / LPR;
+    constexpr int UN = 4;
+    constexpr int NG = kBlock / LPR;
+    __shared__ float gbins[NG][256];
+    for (int i = threadIdx.x; i < NG * 256; i += kBlock) gbins[i >> 8][i & 255] = 0.f;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, l = lane % LPR, gl = lane - l;
+    float* bins = gbins[threadIdx.x / LPR];
+    const int64_t rows_per_block = int64_t(kBlock / 64) * RPW;
+    for (int64_t v0 = int64_t(blockIdx.x) * rows_per_block; v0 < n_rows;
+         v0 += int64_t(gridDim.x) * rows_per_block) {
+        const int64_t v = v0 + (threadIdx.x >> 6) * RPW + lane / LPR;
+        if (v >= n_rows) continue;
+        const int e0 = ptr[v], e1 = ptr[v + 1];
+        if (e0 == e1) continue;
+        float4 g[NT];
+        const float4* grow = reinterpret_cast<const float4*>(gS + v * lds);
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+            g[k] = (k < T && l < W.kq[k]) ? grow[W.cq[k] + l] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float gwl = l < T ? gw[v * ldw + l] : 0.f;
+        for (int c = e0; c < e1; c += LPR) {
+            int mt, mr;
+            int64_t mrow;
+            float mw;
+            edge_meta<LPR>(E, rel, nullptr, c + l, e1, mt, mrow, mw, mr);
+            (void)mw;
+            const int m = min(LPR, e1 - c);
+            for (int j = 0; j < m; j += UN) {
+                float4 x[UN];
+                int tt[UN], rr[UN];
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int src = gl + min(j + u, m - 1);
+                    tt[u] = __shfl(mt, src, 64);
+                    rr[u] = __shfl(mr, src, 64);
+                    const int64_t rw = __shfl(mrow, src, 64);
+                    const int kq = pick_kq<NT>(W, tt[u]);
+                    x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (l < kq)
+                        x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
+                }
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    float4 gg = g[0];
+#pragma unroll
+                    for (int k = 1; k < NT; ++k)
+                        if (tt[u] == k) gg = g[k];
+                    float d = x[u].x * gg.x + x[u].y * gg.y + x[u].z * gg.z + x[u].w * gg.w;
+                    d = group_sum<LPR>(d);
+                    const float b = __shfl(gwl, gl + tt[u], 64);
+                    if (l == 0 && j + u < m) bins[rr[u]] += d + b;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < n_rel; r += kBlock) {
+        float sr = 0.f;
+        for (int k = 0; k < NG; ++k) sr += gbins[k][r];
+        slab[int64_t(blockIdx.x) * n_rel + r] = sr;
+    }
+}
+
 // ---- layer 0 from the sampler's per-type input sums (relation slots) -------------------------
 // With one relation per (target type, source type) pair (ogbn-mag's schema), the outer hop's
 // sampler (regnn_ns_hop_typed_sums, on its own stream ahead of the model) forms the parameter-free
@@ -449,6 +615,95 @@ int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t
     }
     BWD_CASE(64, 4) BWD_CASE(64, 8) BWD_CASE(128, 4) BWD_CASE(128, 8)
 #undef BWD_CASE
+    return REGNN_EUNSUPPORTED;
+}
+
+// the per-type widths of the _kt entries: every K_t in {64, 128, 256} (REGNN_EUNSUPPORTED
+// otherwise), tables non-null and 16-byte aligned; returns the widest K_t in km, sum K_t in sk
+static int kt_widths(const float* const* tables, const int32_t* K_t, int n_types, Tabs& xt,
+                     Widths& W, int& km, int64_t& sk) {
+    xt = Tabs{};
+    W = Widths{};
+    km = 0;
+    sk = 0;
+    for (int t = 0; t < n_types; ++t) {
+        if (K_t[t] != 64 && K_t[t] != 128 && K_t[t] != 256) return REGNN_EUNSUPPORTED;
+        if (!tables[t] || reinterpret_cast<uintptr_t>(tables[t]) % 16) return REGNN_EINVAL;
+        xt.p[t] = tables[t];
+        W.kq[t] = K_t[t] / 4;
+        W.cq[t] = int(sk / 4);
+        sk += K_t[t];
+        if (K_t[t] > km) km = K_t[t];
+    }
+    return REGNN_OK;
+}
+
+int regnn_ns_typed_agg_kt(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                          const float* rel_table, const int32_t* n_id, const int32_t* ntype,
+                          const int64_t* local, const int32_t* e_type, const int64_t* e_off,
+                          const float* const* tables, int32_t n_types, const int32_t* K_t,
+                          int64_t n_rows, float* S, float* wsum, int64_t ld_s, int64_t ld_w,
+                          hipStream_t stream) {
+    EdgeSrc E;
+    if (!ptr || !rel || !rel_table || !tables || !K_t || !S || !wsum || n_types <= 0 ||
+        n_types > kMT || n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, E))
+        return REGNN_EINVAL;
+    Tabs xt;
+    Widths W;
+    int km;
+    int64_t sk;
+    if (const int rc = kt_widths(tables, K_t, n_types, xt, W, km, sk)) return rc;
+    if (ld_s < sk || ld_s % 4 || reinterpret_cast<uintptr_t>(S) % 16 || ld_w < n_types)
+        return REGNN_EINVAL;
+    if (n_rows == 0) return REGNN_OK;
+    const int lpr = km / 4;
+    const int64_t rpb = int64_t(kBlock / 64) * (64 / lpr);
+    int64_t grid = (n_rows + rpb - 1) / rpb;
+    if (grid > kMaxGrid) grid = kMaxGrid;
+#define AGG_KT_CASE(KK, N)                                                                     \
+    if (km == KK && n_types <= N) {                                                            \
+        hipLaunchKernelGGL((typed_agg_kt_kernel<KK, N>), dim3((unsigned)grid), dim3(kBlock),   \
+                           0, stream, ptr, E, rel, rel_table, xt, W, n_types, n_rows, S, wsum, \
+                           ld_s, ld_w);                                                        \
+        REGNN_LAUNCH_CHECK();                                                                  \
+        return REGNN_OK;                                                                       \
+    }
+    AGG_KT_CASE(64, 4) AGG_KT_CASE(64, 8) AGG_KT_CASE(128, 4) AGG_KT_CASE(128, 8)
+    AGG_KT_CASE(256, 4) AGG_KT_CASE(256, 8)
+#undef AGG_KT_CASE
+    return REGNN_EUNSUPPORTED;
+}
+
+int regnn_ns_typed_agg_kt_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                              const int32_t* n_id, const int32_t* ntype, const int64_t* local,
+                              const int32_t* e_type, const int64_t* e_off,
+                              const float* const* tables, int32_t n_types, const int32_t* K_t,
+                              int64_t n_rows, const float* gS, const float* gw, int64_t ld_s,
+                              int64_t ld_w, float* slab, int32_t n_rel, int32_t slab_rows,
+                              hipStream_t stream) {
+    EdgeSrc E;
+    if (!ptr || !rel || !tables || !K_t || !gS || !gw || !slab || n_types <= 0 ||
+        n_types > kMT || n_rows < 0 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0 ||
+        !edge_src(idx, n_id, ntype, local, e_type, e_off, E))
+        return REGNN_EINVAL;
+    Tabs xt;
+    Widths W;
+    int km;
+    int64_t sk;
+    if (const int rc = kt_widths(tables, K_t, n_types, xt, W, km, sk)) return rc;
+    if (ld_s < sk || ld_s % 4 || reinterpret_cast<uintptr_t>(gS) % 16 || ld_w < n_types)
+        return REGNN_EINVAL;
+#define BWD_KT_CASE(KK, N)                                                                     \
+    if (km == KK && n_types <= N) {                                                            \
+        hipLaunchKernelGGL((typed_agg_kt_bwd_kernel<KK, N>), dim3((unsigned)slab_rows),        \
+                           dim3(kBlock), 0, stream, ptr, E, rel, xt, W, n_types, n_rows, gS,   \
+                           gw, slab, n_rel, ld_s, ld_w);                                       \
+        REGNN_LAUNCH_CHECK();                                                                  \
+        return REGNN_OK;                                                                       \
+    }
+    BWD_KT_CASE(64, 4) BWD_KT_CASE(64, 8) BWD_KT_CASE(128, 4) BWD_KT_CASE(128, 8)
+    BWD_KT_CASE(256, 4) BWD_KT_CASE(256, 8)
+#undef BWD_KT_CASE
     return REGNN_EUNSUPPORTED;
 }
 

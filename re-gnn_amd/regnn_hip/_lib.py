@@ -157,6 +157,15 @@ _SIG = {
     "regnn_typed_linear_fwd": ([P, P, P, I64, I32, P, P, P, I32, I32, P, P], ctypes.c_int),
     "regnn_typed_linear_wgrad": ([P, P, P, I64, I32, P, P, I32, I32, I32, P, P, P, P, P],
                                  ctypes.c_int),
+    "regnn_ns_csc_sort": ([P, I32, P, P, P, I32, I32, P], ctypes.c_int),
+    # one input width per node type (K_t: a host int32 array in K's place)
+    "regnn_ns_typed_agg_kt": ([P, P, P, P, P, P, P, P, P, P, I32, P, I64, P, P, I64, I64, P],
+                              ctypes.c_int),
+    "regnn_ns_typed_agg_kt_bwd": ([P, P, P, P, P, P, P, P, P, I32, P, I64, P, P, I64, I64, P, I32,
+                                   I32, P], ctypes.c_int),
+    "regnn_typed_linear_fwd_kt": ([P, P, P, I64, I32, P, P, P, P, I32, P, P], ctypes.c_int),
+    "regnn_typed_linear_wgrad_kt": ([P, P, P, I64, I32, P, P, I32, P, I32, P, P, P, P, P],
+                                    ctypes.c_int),
 }
 
 for _name, (_args, _ret) in _SIG.items():

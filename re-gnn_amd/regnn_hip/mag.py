@@ -459,8 +459,9 @@ class REGNN(torch.nn.Module):
         """mag/regnn_ns.py:300-326 without per-type masks or host syncs: feats_type 2 gathers
         every node's row from its type's table in one launch (ops.typed_gather) before the shared
         Linear; otherwise each node's row goes through its own type's Linear in one gather-fused
-        MFMA launch over the type-sorted rows (ops.typed_linear). Other shapes: one GEMM against
-        all types' weights + a per-node pick."""
+        MFMA launch over the type-sorted rows (ops.typed_linear; one launch per distinct table
+        width, 64 / 128 / 256). Other shapes: one GEMM against all types' weights + a per-node
+        pick, or as the last resort (CPU tables, a missing type, other widths) a mask per type."""
         tabs = self._type_tables(x_dict)
         if any(torch.is_tensor(x) and x.dtype == torch.bfloat16 for x in x_dict.values()):
             # (no upcast of a whole table here, and the gather-fused Linear reads fp32 rows)
@@ -582,7 +583,8 @@ class REGNN(torch.nn.Module):
         conv = self.convs[0]
         if conv.relation_weight.numel() > 256:
             return None
-        T, K = len(tabs), int(tabs[0].shape[1])
+        # (one width per type, feats_type 5's 256 / 128 / 128 / 128: S_t at column sum_{u<t} K_u)
+        T, SK = len(tabs), sum(int(t.shape[1]) for t in tabs)
         if tab is None:
             tab = ops.rel_tab(conv.relation_weight, conv.scaling_factor)       # :110-111
         # [S | w]: the per-type sums and weight sums as one [n, T K + T] operand, so the
@@ -598,7 +600,7 @@ class REGNN(torch.nn.Module):
         n = blk.n_dst
         # [W_c; b_c; 0] = [W_1ᵀ; ..; W_Tᵀ; b_1; ..; b_T; 0] @ W_0: one concatenation and one x6
         # GEMM (the zero rows of the pad a cached constant), forward and backward
-        pad = Sw.shape[1] - T * K - T
+        pad = Sw.shape[1] - SK - T
         zpad = self._zero_rows(pad, conv.weight.shape[0], conv.weight)
         wb_in = torch.cat([lin.weight.t() for lin in lins] +
                           [lin.bias.view(1, -1) for lin in lins] + ([zpad] if pad else []), 0)

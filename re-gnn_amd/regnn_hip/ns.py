@@ -158,6 +158,7 @@ class DeviceSampler:
         # typed_sums[h]: hop h (meta-only, strided) also forms layer 0's input sums for the
         # fused step (regnn_ns_hop_typed_sums; FusedStep.enable_pre_sums), or None
         self.typed_sums = [None] * len(self.sizes_k)
+        self.csc_sorted = None          # hop 0's index sorted per source (regnn_ns_csc_sort)
         self.hop_strided = [None] * len(self.sizes_k)   # per-hop layout override (run_hops)
         self._csc_jobs = {}
         self._csr_fresh = True
@@ -261,6 +262,12 @@ class DeviceSampler:
             deferred = h if ride else -1
             ride_place = (h, k, not later) if ride else None
             self.meta_fresh[h] = self.edge_meta[h] is not None
+        if self.csc_sorted is not None and not self.csc_deferred[0]:
+            # hop 0's transposed index in a canonical order (what the module path's gather reads:
+            # NSTrainer._setup_module_slot), on the stream that built it
+            _, cptr, cent, _ = self.csc[0]
+            L.call("regnn_ns_csc_sort", L.ptr(self.sizes), 1, L.ptr(cptr), L.ptr(cent),
+                   L.ptr(self.csc_sorted), cptr.numel() - 1, cent.numel(), L.stream())
         # the blocks now hold the CSR layout (readable by exact_adjs / model_blocks) or not
         self._csr_fresh = not strided
 
@@ -1380,7 +1387,12 @@ class NSTrainer:
         if s.blocks[0].csr_idx.numel() <= 32768:
             _, cptr, cent, clong = s.csc[0] or s.enable_csc(0)
             b0 = s.blocks[0]
-            b0.csc, b0.csc_cap = (cptr, cent, clong, s.sizes, 1), s.caps[1]
+            # the gather sums floats in entry order and the build's order inside a source's
+            # segment follows an integer atomic: _sample sorts every segment into `csorted`
+            # (regnn_ns_csc_sort), which is what the layer reads -- the same gradient bits on
+            # every run of a batch
+            s.csc_sorted = csorted = torch.zeros_like(cent)
+            b0.csc, b0.csc_cap = (cptr, csorted, clong, s.sizes, 1), s.caps[1]
             from . import ops as _ops
             # (the layer's backward must take the transposed-index gather: ops._NsSpmm)
             if (MODULE_STRIDED["mode"] != "off" and _ops.NS_CSC["mode"] != "off" and
@@ -1425,7 +1437,9 @@ class NSTrainer:
         """relation slots, 128-wide inputs, <= 4 node types: the module path's outer hop runs as
         the sampler's sums launch (regnn_ns_hop_typed_sums, strided, on the sampler's stream) and
         layer 0 reads the per-type sums (ops.ns_slot_agg) instead of gathering the sampled raw
-        rows on the model's stream (mag.REGNN._typed_first_layer); hop 0 stays CSR."""
+        rows on the model's stream (mag.REGNN._typed_first_layer); hop 0 stays CSR. Tables of one
+        width per type (feats_type 5's 256 / 128 / 128 / 128) do not qualify: the sums launch has
+        one K, so layer 0 gathers their rows itself (regnn_ns_typed_agg_kt)."""
         tabs = getattr(self.model, "_type_tables", lambda _x: None)(self.x_dict)
         T = len(tabs) if tabs else 0
         if (MODULE_PRE_SUMS["mode"] == "off" or not tabs or T > 4 or

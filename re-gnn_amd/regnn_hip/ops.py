@@ -967,24 +967,31 @@ class _NsTypedAgg(torch.autograd.Function):
     """S[v, t] = sum_{e in v, type(src) = t} tab[rel_e] x_src (raw input rows read through n_id /
     node type / local row), w[v, t] = sum of the same tab[rel_e] (regnn_ns_typed_agg), returned
     as one [n_dst, T K + T] tensor [S | w] (ext) or as (S [n_dst, T, K], w [n_dst, T]); backward:
-    the relation-table gradient only (the input tables are data, feats_type 3)."""
+    the relation-table gradient only (the input tables are data, feats_type 3). Tables of one
+    width per type (each 64 / 128 / 256; regnn_ns_typed_agg_kt): [n_dst, sum K_t + Tp] with S_t at
+    column sum_{u<t} K_u, or (S [n_dst, sum K_t], w [n_dst, T])."""
 
     @staticmethod
     def forward(ctx, tab, blk, n_id, tables, node_type, local_idx, ext):
-        T, K = len(tables), int(tables[0].shape[1])
+        T, Ks = len(tables), [int(t.shape[1]) for t in tables]
+        K, SK = Ks[0], sum(Ks)
+        # one width per type (or an equal width of 256): the _kt entries, S_t at column
+        # sum_{u<t} K_u; equal widths 64 / 128 keep regnn_ns_typed_agg and its [T, K] rows
+        kt = len(set(Ks)) > 1 or K == 256
         dev = tables[0].device
         if ext:
-            # row stride T K + Tp, Tp = T rounded up to 4 (the kernels take 16-byte aligned
+            # row stride sum K_t + Tp, Tp = T rounded up to 4 (the kernels take 16-byte aligned
             # rows); the Tp - T pad columns are zeros, so a GEMM against [W_c; b_c; 0] is exact
             Tp = _ext_pad(T)
-            out = torch.empty(blk.n_dst, T * K + Tp, dtype=torch.float32, device=dev)
+            out = torch.empty(blk.n_dst, SK + Tp, dtype=torch.float32, device=dev)
             if Tp != T:
-                out[:, T * K + T:].zero_()
-            S_ptr, w_ptr, lds, ldw = L.ptr(out), L.ptr(out) + 4 * T * K, T * K + Tp, T * K + Tp
+                out[:, SK + T:].zero_()
+            S_ptr, w_ptr, lds, ldw = L.ptr(out), L.ptr(out) + 4 * SK, SK + Tp, SK + Tp
         else:
-            S = torch.empty(blk.n_dst, T, K, dtype=torch.float32, device=dev)
+            S = torch.empty((blk.n_dst, SK) if kt else (blk.n_dst, T, K), dtype=torch.float32,
+                            device=dev)
             w = torch.empty(blk.n_dst, T, dtype=torch.float32, device=dev)
-            S_ptr, w_ptr, lds, ldw = L.ptr(S), L.ptr(w), T * K, T
+            S_ptr, w_ptr, lds, ldw = L.ptr(S), L.ptr(w), SK, T
         t = tab.detach().float().contiguous()
         meta = getattr(blk, "edge_meta", None)
         if meta is not None:
@@ -997,10 +1004,13 @@ class _NsTypedAgg(torch.autograd.Function):
             local_idx = _cached_cast(local_idx, torch.int64)
             e_type = e_off = None
         arr = _ptr_array([L.ptr(x) for x in tables])
-        with timed("ns_typed_agg", blk.E * (4 * K + 13) + blk.n_dst * (T * 4 * K + 4 * T + 8)):
-            L.call("regnn_ns_typed_agg", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx), L.ptr(blk.rel),
+        ctx.widths = (ctypes.c_int32 * T)(*Ks) if kt else K
+        with timed("ns_typed_agg", blk.E * (4 * max(Ks) + 13) + blk.n_dst * (4 * SK + 4 * T + 8)):
+            L.call("regnn_ns_typed_agg_kt" if kt else "regnn_ns_typed_agg", L.ptr(blk.csr_ptr),
+                   L.ptr(blk.csr_idx), L.ptr(blk.rel),
                    L.ptr(t), L.ptr(n_id), L.ptr(node_type), L.ptr(local_idx), L.ptr(e_type),
-                   L.ptr(e_off), arr, T, K, blk.n_dst, S_ptr, w_ptr, lds, ldw, L.stream())
+                   L.ptr(e_off), arr, T, ctx.widths, blk.n_dst, S_ptr, w_ptr, lds, ldw,
+                   L.stream())
         ctx.blk, ctx.tables, ctx.idx = blk, tables, (n_id, node_type, local_idx, e_type, e_off)
         ctx.n_rel, ctx.tab_shape, ctx.ext = t.numel(), tab.shape, bool(ext)
         return out if ext else (S, w)
@@ -1011,28 +1021,31 @@ class _NsTypedAgg(torch.autograd.Function):
             return (None,) * 7
         blk, tables = ctx.blk, ctx.tables
         n_id, node_type, local_idx, e_type, e_off = ctx.idx
-        T, K = len(tables), int(tables[0].shape[1])
+        T, Ks = len(tables), [int(t.shape[1]) for t in tables]
+        SK, kt = sum(Ks), not isinstance(ctx.widths, int)
         dev = tables[0].device
         if ctx.ext:
             g = grads[0]
             Tp = _ext_pad(T)
-            g = (torch.zeros(blk.n_dst, T * K + Tp, device=dev) if g is None
+            g = (torch.zeros(blk.n_dst, SK + Tp, device=dev) if g is None
                  else g.contiguous().float())
-            gS_ptr, gw_ptr, lds, ldw = L.ptr(g), L.ptr(g) + 4 * T * K, T * K + Tp, T * K + Tp
+            gS_ptr, gw_ptr, lds, ldw = L.ptr(g), L.ptr(g) + 4 * SK, SK + Tp, SK + Tp
         else:
             gS, gw = grads
-            gS = (torch.zeros(blk.n_dst, T, K, device=dev) if gS is None
+            gS = (torch.zeros(blk.n_dst, SK, device=dev) if gS is None
                   else gS.contiguous().float())
             gw = torch.zeros(blk.n_dst, T, device=dev) if gw is None else gw.contiguous().float()
-            gS_ptr, gw_ptr, lds, ldw = L.ptr(gS), L.ptr(gw), T * K, T
+            gS_ptr, gw_ptr, lds, ldw = L.ptr(gS), L.ptr(gw), SK, T
         rows = L.slab_rows()
         slab = torch.empty(rows, ctx.n_rel, dtype=torch.float32, device=dev)
-        with timed("ns_typed_agg_bwd", blk.E * (4 * K + 13) + blk.n_dst * (T * 4 * K + 4 * T + 8)):
-            L.call("regnn_ns_typed_agg_bwd", L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
+        with timed("ns_typed_agg_bwd",
+                   blk.E * (4 * max(Ks) + 13) + blk.n_dst * (4 * SK + 4 * T + 8)):
+            L.call("regnn_ns_typed_agg_kt_bwd" if kt else "regnn_ns_typed_agg_bwd",
+                   L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
                    L.ptr(blk.rel), L.ptr(n_id), L.ptr(node_type), L.ptr(local_idx),
                    L.ptr(e_type), L.ptr(e_off),
-                   _ptr_array([L.ptr(x) for x in tables]), T, K, blk.n_dst, gS_ptr, gw_ptr,
-                   lds, ldw, L.ptr(slab), ctx.n_rel, rows, L.stream())
+                   _ptr_array([L.ptr(x) for x in tables]), T, ctx.widths, blk.n_dst, gS_ptr,
+                   gw_ptr, lds, ldw, L.ptr(slab), ctx.n_rel, rows, L.stream())
         return _reduce(slab, ctx.n_rel).view(ctx.tab_shape), None, None, None, None, None, None
 
 
@@ -1113,27 +1126,33 @@ def ns_typed_agg(blk, tab, n_id, tables, node_type, local_idx, ext=False):
     mag/regnn_ns.py:300-326 + mag/regnn_layers.py:101-148): returns S [n_dst, T, K] and the
     per-type weight sums w [n_dst, T], or with ext one [n_dst, T K + Tp] tensor [S | w | 0]
     (Tp = T rounded up to 4, zero pad columns: the projection's single GEMM operand against
-    [W_c; b_c; 0]); differentiable in tab."""
+    [W_c; b_c; 0]); differentiable in tab. Tables of one width per type (fp32, each 64 / 128 /
+    256): S [n_dst, sum K_t] with S_t at column sum_{u<t} K_u, ext [n_dst, sum K_t + Tp]."""
     return _NsTypedAgg.apply(tab, blk, n_id, tables, node_type, local_idx, bool(ext))
 
 
-def ns_typed_agg_ok(tables, pre_sums=False):
-    """regnn_ns_typed_agg's operand contract: 1..8 fp32 contiguous device tables of one width
-    64 or 128. pre_sums: layer 0 reads the sampler's per-type input sums (ns_slot_agg over
-    blk.pre_sums), never the tables, which may then also all be bf16 at the sums launch's shapes
-    (regnn_ns_hop_typed_sums_dt: width 128, <= 4 tables)."""
+def typed_agg_layout_ok(tables, pre_sums=False):
+    """the shapes and dtypes ns_typed_agg takes, whatever device the tables are on: 1..8 2-d fp32
+    tables, each 64, 128 or 256 wide (one width per type: regnn_ns_typed_agg_kt; an equal width
+    of 64 / 128: regnn_ns_typed_agg). pre_sums: layer 0 reads the sampler's per-type input sums
+    (ns_slot_agg over blk.pre_sums), never the tables, which may then also all be bf16 at the
+    sums launch's shapes (regnn_ns_hop_typed_sums_dt: equal width 128, <= 4 tables)."""
     if not tables or len(tables) > 8 or any(t is None for t in tables):
         return False
-    K = tables[0].shape[1] if tables[0].dim() == 2 else -1
     dt = tables[0].dtype
-    if dt == torch.bfloat16:
-        if not pre_sums or K != 128 or len(tables) > 4:
-            return False
-    elif dt != torch.float32:
+    if any(t.dtype != dt or t.dim() != 2 for t in tables):
         return False
-    return K in (64, 128) and all(
-        t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[1] == K and
-        t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tables)
+    Ks = [int(t.shape[1]) for t in tables]
+    if dt == torch.bfloat16:
+        return bool(pre_sums) and set(Ks) == {128} and len(tables) <= 4
+    return dt == torch.float32 and all(K in (64, 128, 256) for K in Ks)
+
+
+def ns_typed_agg_ok(tables, pre_sums=False):
+    """regnn_ns_typed_agg's / _kt's operand contract: typed_agg_layout_ok's shapes as contiguous,
+    16-byte aligned device tables."""
+    return typed_agg_layout_ok(tables, pre_sums) and all(
+        t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tables)
 
 
 class _RelTab(torch.autograd.Function):
@@ -2268,15 +2287,22 @@ class _TypedLinear(torch.autograd.Function):
         dev = Ws[0].device
         Y = torch.empty(n, O, dtype=torch.float32, device=dev)
         T = len(tables)
+        Ks = [int(t.shape[1]) for t in tables]
+        # one width per type: regnn_typed_linear_fwd_kt (a launch per distinct width)
+        kt = len(set(Ks)) > 1
+        ctx.widths = (ctypes.c_int32 * T)(*Ks) if kt else K
         Wd = [W.detach().contiguous() for W in Ws]
         bd = [None if b is None else b.detach().contiguous() for b in bs]
-        with timed("typed_linear", n * (K + O) * 4):
-            L.call("regnn_typed_linear_fwd", L.ptr(order), L.ptr(src), L.ptr(off), n, T,
+        with timed("typed_linear", n * (max(Ks) + O) * 4):
+            L.call("regnn_typed_linear_fwd_kt" if kt else "regnn_typed_linear_fwd", L.ptr(order),
+                   L.ptr(src), L.ptr(off), n, T,
                    _ptr_array([L.ptr(t) for t in tables]),
                    _ptr_array([L.ptr(Wd[wg[t]]) for t in range(T)]),
-                   _ptr_array([L.ptr(bd[wg[t]]) for t in range(T)]), K, O, L.ptr(Y), L.stream())
+                   _ptr_array([L.ptr(bd[wg[t]]) for t in range(T)]), ctx.widths, O, L.ptr(Y),
+                   L.stream())
         ctx.plan, ctx.tables, ctx.wg, ctx.G = plan, tables, wg, G
         ctx.shape = (O, K)
+        ctx.gk = [int(W.shape[1]) for W in Ws]
         ctx.has_b = [b is not None for b in bs]
         return Y
 
@@ -2285,39 +2311,54 @@ class _TypedLinear(torch.autograd.Function):
         order, src, off, n = ctx.plan
         G, (O, K) = ctx.G, ctx.shape
         T = len(ctx.tables)
+        kt = not isinstance(ctx.widths, int)
         gY = gY.contiguous().float()
         dev = gY.device
-        gW = [torch.empty(O, K, dtype=torch.float32, device=dev) for _ in range(G)]
+        gW = [torch.empty(O, k, dtype=torch.float32, device=dev) for k in ctx.gk]
         gb = [torch.empty(O, dtype=torch.float32, device=dev) if hb else None
               for hb in ctx.has_b]
-        slab = torch.empty(L.typed_slab_floats(n, T, K, O), dtype=torch.float32, device=dev)
-        with timed("typed_wgrad", n * (K + O) * 4):
-            L.call("regnn_typed_linear_wgrad", L.ptr(order), L.ptr(src), L.ptr(off), n, T,
+        # (mixed widths: every chunk of the slab takes the widest type's O (K + 1) floats)
+        slab = torch.empty(L.typed_slab_floats(n, T, max(ctx.gk), O), dtype=torch.float32,
+                           device=dev)
+        with timed("typed_wgrad", n * (max(ctx.gk) + O) * 4):
+            L.call("regnn_typed_linear_wgrad_kt" if kt else "regnn_typed_linear_wgrad",
+                   L.ptr(order), L.ptr(src), L.ptr(off), n, T,
                    _ptr_array([L.ptr(t) for t in ctx.tables]), (ctypes.c_int32 * T)(*ctx.wg),
-                   G, K, O, L.ptr(gY), L.ptr(slab), _ptr_array([L.ptr(x) for x in gW]),
+                   G, ctx.widths, O, L.ptr(gY), L.ptr(slab), _ptr_array([L.ptr(x) for x in gW]),
                    _ptr_array([L.ptr(x) for x in gb]), L.stream())
         return (None, None, None, None, *gW, *gb)
 
 
 def typed_linear_fusable(tables, weights, biases):
-    """regnn_typed_linear's shapes: <= 8 types, every table fp32 contiguous [*, K] on the device
-    with no gradient, K in {64, 128, 256}, weights [O, K] with O a multiple of 64."""
+    """regnn_typed_linear's shapes: <= 8 types, every table fp32 contiguous [*, K_t] on the device
+    with no gradient, K_t in {64, 128, 256} (one width for all: regnn_typed_linear_fwd / _wgrad;
+    one per type: the _kt entries), weights [O, K_t] with O a multiple of 64 (one per type; with
+    weight groups one per group, as wide as its types' tables)."""
     if not 0 < len(tables) <= 8 or any(t is None for t in tables):
         return False
-    K = tables[0].shape[1]
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+               and not t.requires_grad for t in tables):
+        return False
+    Ks = [int(t.shape[1]) for t in tables]
     O = weights[0].shape[0]
-    return (K in (64, 128, 256) and O % 64 == 0
-            and all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == K
-                    and t.is_contiguous() and not t.requires_grad for t in tables)
-            and all(W.shape == (O, K) and W.dtype == torch.float32 for W in weights)
+    if len(weights) == len(tables):
+        w_ok = all(W.shape == (O, K) for W, K in zip(weights, Ks))
+    else:
+        w_ok = all(W.dim() == 2 and W.shape[0] == O and W.shape[1] in Ks for W in weights)
+    return (all(K in (64, 128, 256) for K in Ks) and O % 64 == 0 and w_ok
+            and all(W.dtype == torch.float32 for W in weights)
             and all(b is None or (b.shape == (O,) and b.dtype == torch.float32) for b in biases))
 
 
 def typed_linear(tables, weights, biases, node_type, local_idx, n_id=None, wgroup=None):
     """tables[t][local] @ weights[g(t)].T + biases[g(t)] for every node of n_id (wgroup: type ->
-    weight index, default the identity): group_input's per-type Linear over the sampled nodes."""
+    weight index, default the identity): group_input's per-type Linear over the sampled nodes.
+    The tables may differ in width (typed_linear_fusable); a weight group then joins types of one
+    width only."""
     T = len(tables)
     wg = list(range(T)) if wgroup is None else [int(g) for g in wgroup]
+    if any(weights[g].shape[1] != tables[t].shape[1] for t, g in enumerate(wg)):
+        raise ValueError("typed_linear: a weight's width differs from its type's table")
     plan = typed_plan(node_type, local_idx, n_id, T)
     return _TypedLinear.apply(plan, [t.contiguous() for t in tables], wg, len(weights),
                               *weights, *biases)
