@@ -1070,7 +1070,8 @@ int regnn_mag_attn_epilogue(const float* acc, const float* rmax, const float* rs
  * hop's per-edge source node type and table row, regnn_ns_hop) the edge's type and row are read
  * from them and idx / n_id / ntype / local may be null. The caller projects
  * a = inv (S W_c + wsum b_c) + bias with W_c[t] = W_t^T W_0, b_c[t] = b_t W_0 (linearity).
- * K in {64, 128} fp32 (rows 16-byte aligned), 1 <= n_types <= 8, tables[t] non-null. Row
+ * K in {64, 128} fp32, 1 <= n_types <= 8, tables[t] non-null and 16-byte aligned (both entries
+ * read them with 16-byte loads: a misaligned table is REGNN_EINVAL, as in the _kt entries). Row
  * strides: S row v at S + v ld_s (ld_s >= n_types K, a multiple of 4, S 16-byte aligned), wsum row v
  * at wsum + v ld_w (ld_w >= n_types): the caller can place wsum as S's last n_types columns
  * (one [n][T K + T] operand, so the projection is one GEMM against [W_c; b_c]). */
@@ -1114,7 +1115,7 @@ int regnn_ns_slot_agg_bwd(const int32_t* sizes, int32_t hop, const float* U, con
 /* Relation-table gradient of regnn_ns_typed_agg: slab[b][r] = block b's partial of
  * sum_{e: rel_e = r} (<tables[t_e][row_e], gS[v][t_e]> + gw[v][t_e]) (per row group bins added
  * in entry order, the groups in a fixed order: bitwise reproducible). Launches slab_rows blocks;
- * reduce the slab with regnn_rel_reduce. n_rel <= 256. */
+ * reduce the slab with regnn_rel_reduce. n_rel <= 256; tables[t] 16-byte aligned (REGNN_EINVAL). */
 int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
                            const int32_t* n_id, const int32_t* ntype, const int64_t* local,
                            const int32_t* e_type, const int64_t* e_off,

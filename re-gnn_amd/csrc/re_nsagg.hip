@@ -13,16 +13,17 @@
 // the backward, the relation-table gradient
 //     d tab[r] = sum_{e: r_e = r} (<x_src_e, gS_v,t(e)> + gw_v,t(e)).
 // The GEMMs (S W_c, its two backward products) stay on hipBLASLt.
+//
+// One forward and one backward body; the tables' widths are their compile-time policy: one K for
+// every type (typed_agg_kernel / _bwd_kernel, K in {64, 128}) or one K_t per type
+// (typed_agg_kt_kernel / _kt_bwd_kernel, widest K_t in {64, 128, 256}); one host launch function
+// per direction.
 #include "regnn_common.h"
 
 namespace regnn {
 namespace nsagg {
 
-constexpr int kMT = 8;                     // node types (REGNN_NSM_MAX_TYPES)
-
-struct Tabs {
-    const float* p[kMT];
-};
+constexpr int kMT = REGNN_NSM_MAX_TYPES;   // node types
 
 template <int N>
 __device__ __forceinline__ const float* pick_tab(const Tabs& t, int i) {
@@ -61,14 +62,49 @@ __device__ __forceinline__ void edge_meta(const EdgeSrc& E, const uint8_t* rel, 
     }
 }
 
-// S [n_rows][T][K] (row stride lds floats), w [n_rows][T] (row stride ldw). LPR = K / 4 lanes
-// per row, 64 / LPR rows per wave.
-template <int K, int NT>
-__global__ void __launch_bounds__(kBlock)
-typed_agg_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
-                 const float* __restrict__ tab, Tabs xt, int T, int64_t n_rows,
-                 float* __restrict__ S, float* __restrict__ wsum, int64_t lds, int64_t ldw) {
-    constexpr int LPR = K / 4;
+// The width policy of the two bodies below: kq(t) float4 per row of table t, cq(t) S_t's first
+// float4 in an output row. With EqualWidths kq is the constant LPR: the `l < kq` predicates and the
+// select chain fold away (load index rw * LPR + l, store index k * LPR + l, no widths among the
+// kernel's arguments).
+template <int LPR>
+struct EqualWidths {               // every table 4 LPR floats wide: S row v is [T][K]
+    __device__ __forceinline__ int kq(int) const { return LPR; }
+    __device__ __forceinline__ int cq(int t) const { return t * LPR; }
+};
+
+// One input width per node type (feats_type 5: paper rows 256 wide, the others 128): tables of
+// widths K_t in {64, 128, 256}, S row v is [S_0 (K_0) | S_1 (K_1) | ..], S_t at column c_t =
+// sum_{u < t} K_u. LPR = KM / 4 lanes per row for the widest table KM; an edge of type t is read by
+// the group's first K_t / 4 lanes (one float4 each), the others sit the load out and add zeros to
+// an accumulator that is never stored.
+struct Widths {
+    int kq[kMT];               // K_t / 4
+    int cq[kMT];               // c_t / 4
+};
+
+template <int NT>
+struct TypeWidths {
+    const Widths& W;
+    // a select chain over the NT widths (a dynamically indexed kernel argument goes to scratch)
+    __device__ __forceinline__ int kq(int t) const {
+        int r = W.kq[0];
+#pragma unroll
+        for (int k = 1; k < NT; ++k)
+            if (t == k) r = W.kq[k];
+        return r;
+    }
+    __device__ __forceinline__ int cq(int t) const { return W.cq[t]; }     // t: an unrolled index
+};
+
+// S [n_rows][sum K_t] (row stride lds floats), w [n_rows][T] (row stride ldw). LPR lanes per row,
+// 64 / LPR rows per wave. Lane l keeps columns 4 l .. 4 l + 3 of every S_t, summed by fmaf in
+// entry order: the two policies give the same bits where all K_t = 4 LPR.
+template <int LPR, int NT, class WP>
+__device__ __forceinline__ void
+typed_agg_rows(const WP& Wd, const int32_t* __restrict__ ptr, const EdgeSrc& E,
+               const uint8_t* __restrict__ rel, const float* __restrict__ tab, const Tabs& xt,
+               int T, int64_t n_rows, float* __restrict__ S, float* __restrict__ wsum,
+               int64_t lds, int64_t ldw) {
     constexpr int RPW = 64 / LPR;
     constexpr int UN = 4;
     const int lane = threadIdx.x & 63, l = lane % LPR, gl = lane - l;
@@ -101,7 +137,10 @@ typed_agg_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __re
                     tt[u] = __shfl(mt, src, 64);
                     const int64_t rw = __shfl(mrow, src, 64);
                     ww[u] = j + u < m ? __shfl(mw, src, 64) : 0.f;
-                    x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * LPR + l];
+                    const int kq = Wd.kq(tt[u]);
+                    x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (l < kq)
+                        x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
                 }
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
@@ -121,7 +160,7 @@ typed_agg_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __re
         float4* srow = reinterpret_cast<float4*>(S + v * lds);
 #pragma unroll
         for (int k = 0; k < NT; ++k)
-            if (k < T) srow[k * LPR + l] = acc[k];
+            if (k < T && l < Wd.kq(k)) srow[Wd.cq(k) + l] = acc[k];
         if (l < T) {
             float s = ws[0];
 #pragma unroll
@@ -132,95 +171,13 @@ typed_agg_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __re
     }
 }
 
-// d tab[r] = sum_e <x_src_e, gS[v, t_e]> + gw[v, t_e]: relation bins per row group in LDS (lane 0
-// of the group adds its entries in order; the group rows summed in group order), one slab row
-// [n_rel] per block (the caller reduces the slab in a fixed order): bitwise reproducible
 template <int K, int NT>
 __global__ void __launch_bounds__(kBlock)
-typed_agg_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
-                     Tabs xt, int T, int64_t n_rows, const float* __restrict__ gS,
-                     const float* __restrict__ gw, float* __restrict__ slab, int n_rel,
-                     int64_t lds, int64_t ldw) {
-    constexpr int LPR = K / 4;
-    constexpr int RPW = 64 / LPR;
-    constexpr int UN = 4;
-    constexpr int NG = kBlock / LPR;
-    __shared__ float gbins[NG][256];
-    for (int i = threadIdx.x; i < NG * 256; i += kBlock) gbins[i >> 8][i & 255] = 0.f;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, l = lane % LPR, gl = lane - l;
-    float* bins = gbins[threadIdx.x / LPR];
-    const int64_t rows_per_block = int64_t(kBlock / 64) * RPW;
-    for (int64_t v0 = int64_t(blockIdx.x) * rows_per_block; v0 < n_rows;
-         v0 += int64_t(gridDim.x) * rows_per_block) {
-        const int64_t v = v0 + (threadIdx.x >> 6) * RPW + lane / LPR;
-        if (v >= n_rows) continue;
-        const int e0 = ptr[v], e1 = ptr[v + 1];
-        if (e0 == e1) continue;
-        float4 g[NT];
-        const float4* grow = reinterpret_cast<const float4*>(gS + v * lds);
-#pragma unroll
-        for (int k = 0; k < NT; ++k) g[k] = k < T ? grow[k * LPR + l] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float gwl = l < T ? gw[v * ldw + l] : 0.f;
-        for (int c = e0; c < e1; c += LPR) {
-            int mt, mr;
-            int64_t mrow;
-            float mw;
-            edge_meta<LPR>(E, rel, nullptr, c + l, e1, mt, mrow, mw, mr);
-            (void)mw;
-            const int m = min(LPR, e1 - c);
-            for (int j = 0; j < m; j += UN) {
-                float4 x[UN];
-                int tt[UN], rr[UN];
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int src = gl + min(j + u, m - 1);
-                    tt[u] = __shfl(mt, src, 64);
-                    rr[u] = __shfl(mr, src, 64);
-                    const int64_t rw = __shfl(mrow, src, 64);
-                    x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * LPR + l];
-                }
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    float4 gg = g[0];
-#pragma unroll
-                    for (int k = 1; k < NT; ++k)
-                        if (tt[u] == k) gg = g[k];
-                    float d = x[u].x * gg.x + x[u].y * gg.y + x[u].z * gg.z + x[u].w * gg.w;
-                    d = group_sum<LPR>(d);
-                    const float b = __shfl(gwl, gl + tt[u], 64);
-                    if (l == 0 && j + u < m) bins[rr[u]] += d + b;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int r = threadIdx.x; r < n_rel; r += kBlock) {
-        float sr = 0.f;
-        for (int k = 0; k < NG; ++k) sr += gbins[k][r];
-        slab[int64_t(blockIdx.x) * n_rel + r] = sr;
-    }
-}
-
-// ---- one input width per node type (feats_type 5: paper rows 256 wide, the others 128) -------
-// The same sums over tables of widths K_t in {64, 128, 256}: S row v is [S_0 (K_0) | S_1 (K_1) |
-// ..], S_t at column c_t = sum_{u < t} K_u. LPR = KM / 4 lanes per row for the widest table KM;
-// an edge of type t is read by the group's first K_t / 4 lanes (one float4 each), the others sit
-// the load out and add zeros to an accumulator that is never stored. Lane l keeps columns
-// 4 l .. 4 l + 3 of every S_t, summed by fmaf in entry order as typed_agg_kernel does: with all
-// K_t = KM the two kernels give the same bits.
-struct Widths {
-    int kq[kMT];               // K_t / 4: float4 per row of table t
-    int cq[kMT];               // c_t / 4: S_t's first float4 in an output row
-};
-
-template <int N>
-__device__ __forceinline__ int pick_kq(const Widths& w, int i) {
-    int r = w.kq[0];
-#pragma unroll
-    for (int k = 1; k < N; ++k)
-        if (i == k) r = w.kq[k];
-    return r;
+typed_agg_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
+                 const float* __restrict__ tab, Tabs xt, int T, int64_t n_rows,
+                 float* __restrict__ S, float* __restrict__ wsum, int64_t lds, int64_t ldw) {
+    typed_agg_rows<K / 4, NT>(EqualWidths<K / 4>{}, ptr, E, rel, tab, xt, T, n_rows, S, wsum, lds,
+                              ldw);
 }
 
 template <int KM, int NT>
@@ -228,88 +185,45 @@ __global__ void __launch_bounds__(kBlock)
 typed_agg_kt_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
                     const float* __restrict__ tab, Tabs xt, Widths W, int T, int64_t n_rows,
                     float* __restrict__ S, float* __restrict__ wsum, int64_t lds, int64_t ldw) {
-    constexpr int LPR = KM / 4;
-    constexpr int RPW = 64 / LPR;
-    constexpr int UN = 4;
-    const int lane = threadIdx.x & 63, l = lane % LPR, gl = lane - l;
-    const int64_t rows_per_block = int64_t(kBlock / 64) * RPW;
-    for (int64_t v0 = int64_t(blockIdx.x) * rows_per_block; v0 < n_rows;
-         v0 += int64_t(gridDim.x) * rows_per_block) {
-        const int64_t v = v0 + (threadIdx.x >> 6) * RPW + lane / LPR;
-        if (v >= n_rows) continue;
-        float4 acc[NT];
-        float ws[NT];
-#pragma unroll
-        for (int k = 0; k < NT; ++k) {
-            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            ws[k] = 0.f;
-        }
-        const int e0 = ptr[v], e1 = ptr[v + 1];
-        for (int c = e0; c < e1; c += LPR) {
-            int mt, mr;
-            int64_t mrow;
-            float mw;
-            edge_meta<LPR>(E, rel, tab, c + l, e1, mt, mrow, mw, mr);
-            const int m = min(LPR, e1 - c);
-            for (int j = 0; j < m; j += UN) {
-                float4 x[UN];
-                int tt[UN];
-                float ww[UN];
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    const int src = gl + min(j + u, m - 1);
-                    tt[u] = __shfl(mt, src, 64);
-                    const int64_t rw = __shfl(mrow, src, 64);
-                    ww[u] = j + u < m ? __shfl(mw, src, 64) : 0.f;
-                    const int kq = pick_kq<NT>(W, tt[u]);
-                    x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (l < kq)
-                        x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
-                }
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-#pragma unroll
-                    for (int k = 0; k < NT; ++k) {
-                        if (tt[u] == k) {
-                            acc[k].x = fmaf(ww[u], x[u].x, acc[k].x);
-                            acc[k].y = fmaf(ww[u], x[u].y, acc[k].y);
-                            acc[k].z = fmaf(ww[u], x[u].z, acc[k].z);
-                            acc[k].w = fmaf(ww[u], x[u].w, acc[k].w);
-                            ws[k] += ww[u];
-                        }
-                    }
-                }
-            }
-        }
-        float4* srow = reinterpret_cast<float4*>(S + v * lds);
-#pragma unroll
-        for (int k = 0; k < NT; ++k)
-            if (k < T && l < W.kq[k]) srow[W.cq[k] + l] = acc[k];
-        if (l < T) {
-            float s = ws[0];
-#pragma unroll
-            for (int k = 1; k < NT; ++k)
-                if (l == k) s = ws[k];
-            wsum[v * ldw + l] = s;
-        }
+    typed_agg_rows<KM / 4, NT>(TypeWidths<NT>{W}, ptr, E, rel, tab, xt, T, n_rows, S, wsum, lds,
+                               ldw);
+}
+
+// The relation bins of the backward kernels: one [256] row per row group in LDS, zeroed first ...
+template <int NG>
+__device__ __forceinline__ void bins_zero(float (&gbins)[NG][256]) {
+    for (int i = threadIdx.x; i < NG * 256; i += kBlock) gbins[i >> 8][i & 255] = 0.f;
+    __syncthreads();
+}
+
+// ... and summed in group order into the block's slab row [n_rel] after the rows
+template <int NG>
+__device__ __forceinline__ void bins_store(const float (&gbins)[NG][256], float* __restrict__ slab,
+                                           int n_rel) {
+    __syncthreads();
+    for (int r = threadIdx.x; r < n_rel; r += kBlock) {
+        float sr = 0.f;
+        for (int k = 0; k < NG; ++k) sr += gbins[k][r];
+        slab[int64_t(blockIdx.x) * n_rel + r] = sr;
     }
 }
 
-// its relation-table gradient, in typed_agg_bwd_kernel's slab form (per-group LDS bins, no float
-// atomics); the dot's butterfly runs over KM / 4 lanes, the lanes past K_t / 4 adding zeros
-template <int KM, int NT>
-__global__ void __launch_bounds__(kBlock)
-typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
-                        const uint8_t* __restrict__ rel, Tabs xt, Widths W, int T, int64_t n_rows,
-                        const float* __restrict__ gS, const float* __restrict__ gw,
-                        float* __restrict__ slab, int n_rel, int64_t lds, int64_t ldw) {
-    constexpr int LPR = KM / 4;
+// d tab[r] = sum_e <x_src_e, gS[v, t_e]> + gw[v, t_e]: relation bins per row group in LDS (lane 0
+// of the group adds its entries in order; the group rows summed in group order), one slab row
+// [n_rel] per block (the caller reduces the slab in a fixed order): bitwise reproducible, no float
+// atomics. The dot's butterfly runs over LPR lanes, with TypeWidths the lanes past K_t / 4 adding
+// zeros: the per-type kernel's bits are its own, not the equal-width kernel's.
+template <int LPR, int NT, class WP>
+__device__ __forceinline__ void
+typed_agg_bwd_rows(const WP& Wd, const int32_t* __restrict__ ptr, const EdgeSrc& E,
+                   const uint8_t* __restrict__ rel, const Tabs& xt, int T, int64_t n_rows,
+                   const float* __restrict__ gS, const float* __restrict__ gw,
+                   float* __restrict__ slab, int n_rel, int64_t lds, int64_t ldw) {
     constexpr int RPW = 64 / LPR;
     constexpr int UN = 4;
     constexpr int NG = kBlock / LPR;
     __shared__ float gbins[NG][256];
-    for (int i = threadIdx.x; i < NG * 256; i += kBlock) gbins[i >> 8][i & 255] = 0.f;
-    __syncthreads();
+    bins_zero(gbins);
     const int lane = threadIdx.x & 63, l = lane % LPR, gl = lane - l;
     float* bins = gbins[threadIdx.x / LPR];
     const int64_t rows_per_block = int64_t(kBlock / 64) * RPW;
@@ -323,7 +237,7 @@ typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
         const float4* grow = reinterpret_cast<const float4*>(gS + v * lds);
 #pragma unroll
         for (int k = 0; k < NT; ++k)
-            g[k] = (k < T && l < W.kq[k]) ? grow[W.cq[k] + l] : make_float4(0.f, 0.f, 0.f, 0.f);
+            g[k] = (k < T && l < Wd.kq(k)) ? grow[Wd.cq(k) + l] : make_float4(0.f, 0.f, 0.f, 0.f);
         const float gwl = l < T ? gw[v * ldw + l] : 0.f;
         for (int c = e0; c < e1; c += LPR) {
             int mt, mr;
@@ -341,7 +255,7 @@ typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
                     tt[u] = __shfl(mt, src, 64);
                     rr[u] = __shfl(mr, src, 64);
                     const int64_t rw = __shfl(mrow, src, 64);
-                    const int kq = pick_kq<NT>(W, tt[u]);
+                    const int kq = Wd.kq(tt[u]);
                     x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (l < kq)
                         x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
@@ -352,7 +266,10 @@ typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
 #pragma unroll
                     for (int k = 1; k < NT; ++k)
                         if (tt[u] == k) gg = g[k];
-                    float d = x[u].x * gg.x + x[u].y * gg.y + x[u].z * gg.z + x[u].w * gg.w;
+                    // <x, gg>, fused in the order the compiler gave x.x gg.x + x.y gg.y + .. while
+                    // the choice was its own: written out, so the bits no longer move with it
+                    float d = fmaf(gg.w, x[u].w,
+                                   fmaf(gg.z, x[u].z, fmaf(gg.x, x[u].x, gg.y * x[u].y)));
                     d = group_sum<LPR>(d);
                     const float b = __shfl(gwl, gl + tt[u], 64);
                     if (l == 0 && j + u < m) bins[rr[u]] += d + b;
@@ -360,12 +277,27 @@ typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
             }
         }
     }
-    __syncthreads();
-    for (int r = threadIdx.x; r < n_rel; r += kBlock) {
-        float sr = 0.f;
-        for (int k = 0; k < NG; ++k) sr += gbins[k][r];
-        slab[int64_t(blockIdx.x) * n_rel + r] = sr;
-    }
+    bins_store(gbins, slab, n_rel);
+}
+
+template <int K, int NT>
+__global__ void __launch_bounds__(kBlock)
+typed_agg_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
+                     Tabs xt, int T, int64_t n_rows, const float* __restrict__ gS,
+                     const float* __restrict__ gw, float* __restrict__ slab, int n_rel,
+                     int64_t lds, int64_t ldw) {
+    typed_agg_bwd_rows<K / 4, NT>(EqualWidths<K / 4>{}, ptr, E, rel, xt, T, n_rows, gS, gw, slab,
+                                  n_rel, lds, ldw);
+}
+
+template <int KM, int NT>
+__global__ void __launch_bounds__(kBlock)
+typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
+                        const uint8_t* __restrict__ rel, Tabs xt, Widths W, int T, int64_t n_rows,
+                        const float* __restrict__ gS, const float* __restrict__ gw,
+                        float* __restrict__ slab, int n_rel, int64_t lds, int64_t ldw) {
+    typed_agg_bwd_rows<KM / 4, NT>(TypeWidths<NT>{W}, ptr, E, rel, xt, T, n_rows, gS, gw, slab,
+                                   n_rel, lds, ldw);
 }
 
 // ---- layer 0 from the sampler's per-type input sums (relation slots) -------------------------
@@ -434,8 +366,7 @@ slot_agg_bwd_kernel(const int32_t* __restrict__ sizes, int hop, const float* __r
                     int n_et, int T, float* __restrict__ slab, int n_rel) {
     constexpr int NG = kBlock / 32;
     __shared__ float gbins[NG][256];
-    for (int i = threadIdx.x; i < NG * 256; i += kBlock) gbins[i >> 8][i & 255] = 0.f;
-    __syncthreads();
+    bins_zero(gbins);
     const int n = sizes[hop];
     const int l = threadIdx.x & 31, grp = threadIdx.x / 32;
     float* bins = gbins[grp];
@@ -462,12 +393,7 @@ slot_agg_bwd_kernel(const int32_t* __restrict__ sizes, int hop, const float* __r
             }
         }
     }
-    __syncthreads();
-    for (int r = threadIdx.x; r < n_rel; r += kBlock) {
-        float sr = 0.f;
-        for (int k = 0; k < NG; ++k) sr += gbins[k][r];
-        slab[int64_t(blockIdx.x) * n_rel + r] = sr;
-    }
+    bins_store(gbins, slab, n_rel);
 }
 
 // ---- the mean aggregation of a block in the strided layout (regnn_ns_hop strided = 1) --------
@@ -541,6 +467,91 @@ strided_spmm_kernel(const int32_t* __restrict__ live, const int32_t* __restrict_
 using namespace regnn;
 using namespace regnn::nsagg;
 
+// What the four entries share after their own pointer and range checks (E is theirs, edge_src):
+// the tables, non-null and 16-byte aligned (the kernels read them with 16-byte loads); their
+// widths, K_t[t] per type for the _kt entries (each in {64, 128, 256}: REGNN_EUNSUPPORTED
+// otherwise) or, K_t null, K for every type (any K: the launch refuses what it has no kernel for);
+// the S / gS operand `s`, 16-byte aligned, ld_s >= sum K_t and a multiple of 4, ld_w >= n_types.
+struct AggCall {
+    const int32_t* ptr; EdgeSrc E; const uint8_t* rel; Tabs xt; Widths W;
+    bool per_type;
+    int km, T;                 // the widest table (LPR = km / 4), node types
+    int64_t n_rows, lds, ldw; hipStream_t stream;
+};
+
+static int agg_call(AggCall& c, const int32_t* ptr, const uint8_t* rel,
+                    const float* const* tables, int32_t n_types, const int32_t* K_t, int32_t K,
+                    int64_t n_rows, const float* s, int64_t ld_s, int64_t ld_w,
+                    hipStream_t stream) {
+    c.ptr = ptr, c.rel = rel, c.xt = Tabs{}, c.W = Widths{}, c.per_type = K_t != nullptr;
+    c.km = 0, c.T = n_types, c.n_rows = n_rows, c.lds = ld_s, c.ldw = ld_w, c.stream = stream;
+    int64_t sk = 0;
+    for (int t = 0; t < n_types; ++t) {
+        const int k = K_t ? K_t[t] : K;
+        if (K_t && k != 64 && k != 128 && k != 256) return REGNN_EUNSUPPORTED;
+        if (!tables[t] || reinterpret_cast<uintptr_t>(tables[t]) % 16) return REGNN_EINVAL;
+        c.xt.p[t] = tables[t];
+        c.W.kq[t] = k / 4;
+        c.W.cq[t] = int(sk / 4);
+        sk += k;
+        if (k > c.km) c.km = k;
+    }
+    const bool ok = ld_s >= sk && ld_s % 4 == 0 && reinterpret_cast<uintptr_t>(s) % 16 == 0;
+    return ok && ld_w >= n_types ? REGNN_OK : REGNN_EINVAL;
+}
+
+// One launch per direction. The per-type kernels are built for a widest table of 64, 128 and 256,
+// the equal-width ones for 64 and 128 (an equal width of 256 is the _kt entries').
+template <int KK, int N>
+static int agg_fwd_at(const AggCall& c, const float* tab, float* S, float* wsum) {
+    const int64_t rpb = int64_t(kBlock / 64) * (64 / (KK / 4));
+    const dim3 grid(unsigned(std::min<int64_t>((c.n_rows + rpb - 1) / rpb, kMaxGrid)));
+    if (c.per_type)
+        hipLaunchKernelGGL((typed_agg_kt_kernel<KK, N>), grid, dim3(kBlock), 0, c.stream, c.ptr,
+                           c.E, c.rel, tab, c.xt, c.W, c.T, c.n_rows, S, wsum, c.lds, c.ldw);
+    else if constexpr (KK <= 128)
+        hipLaunchKernelGGL((typed_agg_kernel<KK, N>), grid, dim3(kBlock), 0, c.stream, c.ptr, c.E,
+                           c.rel, tab, c.xt, c.T, c.n_rows, S, wsum, c.lds, c.ldw);
+    else return REGNN_EUNSUPPORTED;
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}
+
+template <int KK, int N>
+static int agg_bwd_at(const AggCall& c, const float* gS, const float* gw, float* slab, int n_rel,
+                      int slab_rows) {
+    if (c.per_type)
+        hipLaunchKernelGGL((typed_agg_kt_bwd_kernel<KK, N>), dim3(unsigned(slab_rows)),
+                           dim3(kBlock), 0, c.stream, c.ptr, c.E, c.rel, c.xt, c.W, c.T, c.n_rows,
+                           gS, gw, slab, n_rel, c.lds, c.ldw);
+    else if constexpr (KK <= 128)
+        hipLaunchKernelGGL((typed_agg_bwd_kernel<KK, N>), dim3(unsigned(slab_rows)), dim3(kBlock),
+                           0, c.stream, c.ptr, c.E, c.rel, c.xt, c.T, c.n_rows, gS, gw, slab,
+                           n_rel, c.lds, c.ldw);
+    else return REGNN_EUNSUPPORTED;
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}
+
+// (widest K, n_types <= 4 / <= 8) -> the instantiation
+#define AGG_DISPATCH(AT, ...)                                                                  \
+    if (c.km == 64) return c.T <= 4 ? AT<64, 4>(__VA_ARGS__) : AT<64, 8>(__VA_ARGS__);         \
+    if (c.km == 128) return c.T <= 4 ? AT<128, 4>(__VA_ARGS__) : AT<128, 8>(__VA_ARGS__);      \
+    if (c.km == 256) return c.T <= 4 ? AT<256, 4>(__VA_ARGS__) : AT<256, 8>(__VA_ARGS__);      \
+    return REGNN_EUNSUPPORTED;
+
+static int agg_fwd(const AggCall& c, const float* tab, float* S, float* wsum) {
+    if (c.n_rows == 0) return REGNN_OK;
+    AGG_DISPATCH(agg_fwd_at, c, tab, S, wsum)
+}
+
+// (no early return at n_rows == 0: the slab's rows are written, as zeros)
+static int agg_bwd(const AggCall& c, const float* gS, const float* gw, float* slab, int n_rel,
+                   int slab_rows) {
+    AGG_DISPATCH(agg_bwd_at, c, gS, gw, slab, n_rel, slab_rows)
+}
+#undef AGG_DISPATCH
+
 extern "C" {
 
 static bool edge_src(const int32_t* idx, const int32_t* n_id, const int32_t* ntype,
@@ -556,34 +567,12 @@ int regnn_ns_typed_agg(const int32_t* ptr, const int32_t* idx, const uint8_t* re
                        const int64_t* local, const int32_t* e_type, const int64_t* e_off,
                        const float* const* tables, int32_t n_types, int32_t K, int64_t n_rows,
                        float* S, float* wsum, int64_t ld_s, int64_t ld_w, hipStream_t stream) {
-    EdgeSrc E;
+    AggCall c;
     if (!ptr || !rel || !rel_table || !tables || !S || !wsum || n_types <= 0 || n_types > kMT ||
-        n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, E))
+        n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    if (ld_s < int64_t(n_types) * K || ld_s % 4 || reinterpret_cast<uintptr_t>(S) % 16 ||
-        ld_w < n_types)
-        return REGNN_EINVAL;
-    Tabs xt{};
-    for (int t = 0; t < n_types; ++t) {
-        if (!tables[t]) return REGNN_EINVAL;
-        xt.p[t] = tables[t];
-    }
-    if (n_rows == 0) return REGNN_OK;
-    const int lpr = K / 4;
-    const int64_t rpb = int64_t(kBlock / 64) * (64 / lpr);
-    int64_t grid = (n_rows + rpb - 1) / rpb;
-    if (grid > kMaxGrid) grid = kMaxGrid;
-#define AGG_CASE(KK, N)                                                                        \
-    if (K == KK && n_types <= N) {                                                             \
-        hipLaunchKernelGGL((typed_agg_kernel<KK, N>), dim3((unsigned)grid), dim3(kBlock), 0,   \
-                           stream, ptr, E, rel, rel_table, xt, n_types, n_rows, S, wsum, ld_s, \
-                           ld_w);                                                              \
-        REGNN_LAUNCH_CHECK();                                                                  \
-        return REGNN_OK;                                                                       \
-    }
-    AGG_CASE(64, 4) AGG_CASE(64, 8) AGG_CASE(128, 4) AGG_CASE(128, 8)
-#undef AGG_CASE
-    return REGNN_EUNSUPPORTED;
+    int rc = agg_call(c, ptr, rel, tables, n_types, nullptr, K, n_rows, S, ld_s, ld_w, stream);
+    return rc ? rc : agg_fwd(c, rel_table, S, wsum);
 }
 
 int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
@@ -592,50 +581,13 @@ int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t
                            const float* const* tables, int32_t n_types, int32_t K, int64_t n_rows,
                            const float* gS, const float* gw, int64_t ld_s, int64_t ld_w,
                            float* slab, int32_t n_rel, int32_t slab_rows, hipStream_t stream) {
-    EdgeSrc E;
+    AggCall c;
     if (!ptr || !rel || !tables || !gS || !gw || !slab || n_types <= 0 || n_types > kMT ||
         n_rows < 0 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0 ||
-        !edge_src(idx, n_id, ntype, local, e_type, e_off, E))
+        !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    if (ld_s < int64_t(n_types) * K || ld_s % 4 || reinterpret_cast<uintptr_t>(gS) % 16 ||
-        ld_w < n_types)
-        return REGNN_EINVAL;
-    Tabs xt{};
-    for (int t = 0; t < n_types; ++t) {
-        if (!tables[t]) return REGNN_EINVAL;
-        xt.p[t] = tables[t];
-    }
-#define BWD_CASE(KK, N)                                                                        \
-    if (K == KK && n_types <= N) {                                                             \
-        hipLaunchKernelGGL((typed_agg_bwd_kernel<KK, N>), dim3((unsigned)slab_rows),           \
-                           dim3(kBlock), 0, stream, ptr, E, rel, xt, n_types, n_rows, gS, gw,  \
-                           slab, n_rel, ld_s, ld_w);                                           \
-        REGNN_LAUNCH_CHECK();                                                                  \
-        return REGNN_OK;                                                                       \
-    }
-    BWD_CASE(64, 4) BWD_CASE(64, 8) BWD_CASE(128, 4) BWD_CASE(128, 8)
-#undef BWD_CASE
-    return REGNN_EUNSUPPORTED;
-}
-
-// the per-type widths of the _kt entries: every K_t in {64, 128, 256} (REGNN_EUNSUPPORTED
-// otherwise), tables non-null and 16-byte aligned; returns the widest K_t in km, sum K_t in sk
-static int kt_widths(const float* const* tables, const int32_t* K_t, int n_types, Tabs& xt,
-                     Widths& W, int& km, int64_t& sk) {
-    xt = Tabs{};
-    W = Widths{};
-    km = 0;
-    sk = 0;
-    for (int t = 0; t < n_types; ++t) {
-        if (K_t[t] != 64 && K_t[t] != 128 && K_t[t] != 256) return REGNN_EUNSUPPORTED;
-        if (!tables[t] || reinterpret_cast<uintptr_t>(tables[t]) % 16) return REGNN_EINVAL;
-        xt.p[t] = tables[t];
-        W.kq[t] = K_t[t] / 4;
-        W.cq[t] = int(sk / 4);
-        sk += K_t[t];
-        if (K_t[t] > km) km = K_t[t];
-    }
-    return REGNN_OK;
+    int rc = agg_call(c, ptr, rel, tables, n_types, nullptr, K, n_rows, gS, ld_s, ld_w, stream);
+    return rc ? rc : agg_bwd(c, gS, gw, slab, n_rel, slab_rows);
 }
 
 int regnn_ns_typed_agg_kt(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
@@ -644,34 +596,12 @@ int regnn_ns_typed_agg_kt(const int32_t* ptr, const int32_t* idx, const uint8_t*
                           const float* const* tables, int32_t n_types, const int32_t* K_t,
                           int64_t n_rows, float* S, float* wsum, int64_t ld_s, int64_t ld_w,
                           hipStream_t stream) {
-    EdgeSrc E;
+    AggCall c;
     if (!ptr || !rel || !rel_table || !tables || !K_t || !S || !wsum || n_types <= 0 ||
-        n_types > kMT || n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, E))
+        n_types > kMT || n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    Tabs xt;
-    Widths W;
-    int km;
-    int64_t sk;
-    if (const int rc = kt_widths(tables, K_t, n_types, xt, W, km, sk)) return rc;
-    if (ld_s < sk || ld_s % 4 || reinterpret_cast<uintptr_t>(S) % 16 || ld_w < n_types)
-        return REGNN_EINVAL;
-    if (n_rows == 0) return REGNN_OK;
-    const int lpr = km / 4;
-    const int64_t rpb = int64_t(kBlock / 64) * (64 / lpr);
-    int64_t grid = (n_rows + rpb - 1) / rpb;
-    if (grid > kMaxGrid) grid = kMaxGrid;
-#define AGG_KT_CASE(KK, N)                                                                     \
-    if (km == KK && n_types <= N) {                                                            \
-        hipLaunchKernelGGL((typed_agg_kt_kernel<KK, N>), dim3((unsigned)grid), dim3(kBlock),   \
-                           0, stream, ptr, E, rel, rel_table, xt, W, n_types, n_rows, S, wsum, \
-                           ld_s, ld_w);                                                        \
-        REGNN_LAUNCH_CHECK();                                                                  \
-        return REGNN_OK;                                                                       \
-    }
-    AGG_KT_CASE(64, 4) AGG_KT_CASE(64, 8) AGG_KT_CASE(128, 4) AGG_KT_CASE(128, 8)
-    AGG_KT_CASE(256, 4) AGG_KT_CASE(256, 8)
-#undef AGG_KT_CASE
-    return REGNN_EUNSUPPORTED;
+    int rc = agg_call(c, ptr, rel, tables, n_types, K_t, 0, n_rows, S, ld_s, ld_w, stream);
+    return rc ? rc : agg_fwd(c, rel_table, S, wsum);
 }
 
 int regnn_ns_typed_agg_kt_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
@@ -681,30 +611,13 @@ int regnn_ns_typed_agg_kt_bwd(const int32_t* ptr, const int32_t* idx, const uint
                               int64_t n_rows, const float* gS, const float* gw, int64_t ld_s,
                               int64_t ld_w, float* slab, int32_t n_rel, int32_t slab_rows,
                               hipStream_t stream) {
-    EdgeSrc E;
+    AggCall c;
     if (!ptr || !rel || !tables || !K_t || !gS || !gw || !slab || n_types <= 0 ||
         n_types > kMT || n_rows < 0 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0 ||
-        !edge_src(idx, n_id, ntype, local, e_type, e_off, E))
+        !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    Tabs xt;
-    Widths W;
-    int km;
-    int64_t sk;
-    if (const int rc = kt_widths(tables, K_t, n_types, xt, W, km, sk)) return rc;
-    if (ld_s < sk || ld_s % 4 || reinterpret_cast<uintptr_t>(gS) % 16 || ld_w < n_types)
-        return REGNN_EINVAL;
-#define BWD_KT_CASE(KK, N)                                                                     \
-    if (km == KK && n_types <= N) {                                                            \
-        hipLaunchKernelGGL((typed_agg_kt_bwd_kernel<KK, N>), dim3((unsigned)slab_rows),        \
-                           dim3(kBlock), 0, stream, ptr, E, rel, xt, W, n_types, n_rows, gS,   \
-                           gw, slab, n_rel, ld_s, ld_w);                                       \
-        REGNN_LAUNCH_CHECK();                                                                  \
-        return REGNN_OK;                                                                       \
-    }
-    BWD_KT_CASE(64, 4) BWD_KT_CASE(64, 8) BWD_KT_CASE(128, 4) BWD_KT_CASE(128, 8)
-    BWD_KT_CASE(256, 4) BWD_KT_CASE(256, 8)
-#undef BWD_KT_CASE
-    return REGNN_EUNSUPPORTED;
+    int rc = agg_call(c, ptr, rel, tables, n_types, K_t, 0, n_rows, gS, ld_s, ld_w, stream);
+    return rc ? rc : agg_bwd(c, gS, gw, slab, n_rel, slab_rows);
 }
 
 int regnn_ns_spmm_strided_fwd(const int32_t* live, const int32_t* cnt, int32_t stride,

@@ -13,6 +13,11 @@ constexpr int kMaxGrid = 2048;    // grid-stride cap (8 blocks per CU); bounds t
 
 using bf16_t = uint16_t;          // storage type for REGNN_BF16 rows
 
+// one fp32 table (or weight, bias, gradient) per node type, passed by value as a kernel argument
+struct Tabs {
+    const float* p[REGNN_NSM_MAX_TYPES];
+};
+
 // fp32 <-> bf16 (round to nearest even via the gfx950 conversion instruction)
 __device__ __forceinline__ float bf2f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
 __device__ __forceinline__ uint16_t f2bf(float f) {

@@ -3,7 +3,7 @@
 
     python tools/ns_widths_time.py [--scale 1] [--batch 512] [--hidden 512] [--steps 20]
                                    [--rounds 7] [--widths 256,128,128,128]
-                                   [--legs eager,captured] [--out FILE]
+                                   [--legs eager,captured] [--kernel-steps 0] [--out FILE]
 
 One graph -- mag_like(scale), REGNN 'regcn' hidden 512, LayerNorm, 349 classes, fan-out [25, 20],
 dropout 0.5, FlatAdam -- and two trainers over it, built through NSTrainer's public arguments only
@@ -19,6 +19,10 @@ After warm-up runs, `rounds` timed windows of `steps` steps each, alternating th
 a host clock around the steps ending in a device synchronise. Prints (and with --out writes) one
 JSON line: each leg's per-step median, min and max over the rounds (us), and whether the trainer
 ran the typed first layer over a meta-only last hop (module_lean).
+--kernel-steps K > 0: after the windows, K more eager steps under regnn_hip.profile's event timers;
+the device time per step of the typed layer-0 operators (ns_typed_agg, ns_typed_agg_bwd,
+typed_linear, typed_wgrad) goes into "kernel_us_per_step". A label the step never launched is
+absent (with the sampler's pre-sums on, equal widths never launch ns_typed_agg).
 """
 import argparse
 import json
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--widths", default="256,128,128,128")
     ap.add_argument("--legs", default="eager,captured")
+    ap.add_argument("--kernel-steps", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -119,6 +124,17 @@ def main():
                   "module_lean": bool(getattr(tr, "_module_lean", False))}
     for k, e in errors.items():
         out[k] = {"error": e}
+    if args.kernel_steps > 0:
+        from regnn_hip import profile
+        profile.enable()
+        for _ in range(args.kernel_steps):
+            tr_e.step()
+        torch.cuda.synchronize()
+        out["kernel_us_per_step"] = {
+            k: round(v[2] * 1e3 / args.kernel_steps, 1)
+            for k, v in sorted(profile.summary().items())
+            if k in ("ns_typed_agg", "ns_typed_agg_bwd", "typed_linear", "typed_wgrad")}
+        profile.enable(False)
     line = json.dumps(out)
     print(line)
     if args.out:
