@@ -782,6 +782,35 @@ int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uin
                                const regnn_ns_csc_job* csc, const regnn_ns_type_layout* layout,
                                hipStream_t stream);
 
+/* regnn_ns_hop_typed_sums_dt with one input width per node type (feats_type 5 of
+ * mag/regnn_ns.py:185-194: paper rows 256 wide, the other types 128; the same reference lines
+ * replaced): `widths` stands where K stood, a host array of n_types ints, each 64, 128 or 256,
+ * read during the call (a captured graph holds its values, as with regnn_ns_type_layout).
+ * tables[t] is [*, widths[t]] of dtype (fp32 or bf16, all tables alike), 16-byte aligned. With
+ * SK = sum widths and KM = max widths:
+ *   s_agg [cap][SK]  type t's unweighted sum at column sum_{u<t} widths[u] (the columns of
+ *                    regnn_ns_typed_agg_kt's S)
+ *   u_self [cap][KM] the self loop's row in the first widths[t_self] columns, zeros after them
+ *                    (every live row rewritten in full by every call)
+ *   s_w [cap][T], u_rel [cap][T + 1], scnt, inv, the optional per-slot meta, sizes and state: as
+ *   regnn_ns_hop_typed_sums_dt writes them -- the sampling does not depend on the widths.
+ * Per (row, type, column) the additions run in the equal-width kernels' order, so with every
+ * width 128 each output holds regnn_ns_hop_typed_sums_dt's bits, and a bf16 table gives the bits of
+ * the fp32 call on the widened table. The csc job, the layout (or the lookup tables) and the
+ * all-NULL meta triple as there. Before any launch: REGNN_EINVAL for NULL widths, a NULL or
+ * misaligned table, another dtype, one or two NULL among blk_rel / edge_type / edge_off;
+ * REGNN_EUNSUPPORTED for a width outside {64, 128, 256}, n_types outside 1..4, k outside 1..63.
+ * Added without an ABI bump (the version stays 51): new symbols only. */
+int regnn_ns_hop_typed_sums_kt(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                               const int32_t* ntype, int32_t num_edge_types, int32_t k,
+                               int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
+                               int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
+                               const int64_t* local, int32_t* edge_type, int64_t* edge_off,
+                               const void* const* tables, int32_t dtype, int32_t n_types,
+                               const int32_t* widths, float* s_agg, float* s_w, float* u_self,
+                               int32_t* u_rel, const regnn_ns_csc_job* csc,
+                               const regnn_ns_type_layout* layout, hipStream_t stream);
+
 /* Backward of a sampled block's aggregation y[v] = out_scale[v] sum_e rel_table[rel_e] x[idx_e]
  * (+ bias) over rows v < n_rows (the forward is regnn_spmm_fwd on the block):
  *   gx[idx_e] += rel_table[rel_e] * out_scale[v] * g[v]   (gx zero-filled by the caller; hardware
@@ -1111,6 +1140,23 @@ int regnn_ns_slot_agg_bwd(const int32_t* sizes, int32_t hop, const float* U, con
                           const float* x_self, const int32_t* u_rel, const float* g, int64_t ld,
                           int32_t n_et, int32_t n_types, int32_t K, float* slab, int32_t n_rel,
                           int32_t slab_rows, hipStream_t stream);
+
+/* regnn_ns_slot_agg / _bwd over regnn_ns_hop_typed_sums_kt's outputs (the same reference lines):
+ * `widths` (a host array of n_types ints, each 64 / 128 / 256) in K's place, U [cap][SK] with
+ * type t at column c_t = sum_{u<t} widths[u], x_self [cap][KM]. The output (and g) row is
+ * [S_0 (K_0) | .. | S_{T-1} (K_{T-1}) | w (Tp)], ld >= SK + Tp: the ext operand of
+ * regnn_ns_typed_agg_kt. The same row rule (zeros in [sizes[hop], next multiple of 128), later
+ * rows untouched), the same slab order; with every width 128 both give regnn_ns_slot_agg's /
+ * _bwd's bits. NULL widths: REGNN_EINVAL; a width outside {64, 128, 256} or n_types > 4:
+ * REGNN_EUNSUPPORTED; the other refusals as above. New symbols, ABI version unchanged. */
+int regnn_ns_slot_agg_kt(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                         const float* x_self, const int32_t* u_rel, const float* rel_table,
+                         int32_t n_et, int32_t n_types, const int32_t* widths, int64_t cap,
+                         float* out, int64_t ld, hipStream_t stream);
+int regnn_ns_slot_agg_bwd_kt(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                             const float* x_self, const int32_t* u_rel, const float* g,
+                             int64_t ld, int32_t n_et, int32_t n_types, const int32_t* widths,
+                             float* slab, int32_t n_rel, int32_t slab_rows, hipStream_t stream);
 
 /* Relation-table gradient of regnn_ns_typed_agg: slab[b][r] = block b's partial of
  * sum_{e: rel_e = r} (<tables[t_e][row_e], gS[v][t_e]> + gw[v][t_e]) (per row group bins added

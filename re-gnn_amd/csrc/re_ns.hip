@@ -1047,6 +1047,285 @@ ns_sample_sums_kernel(NsSumArgs A) {
     }
 }
 
+// The same launch with one input width per node type (feats_type 5: paper rows 256 wide, the
+// others 128), K_t in {64, 128, 256}: s_agg [cap][sum K_t] with type t's sum at column
+// sum_{u<t} K_u (regnn_ns_typed_agg_kt's columns), u_self [cap][max K_t], zeros past the self
+// loop's own width. The widths come by value, packed a byte per type into two words (a
+// dynamically indexed kernel argument would go to scratch, and ten more scalars spilled).
+//
+// A kernel of its own, not a width policy over ns_sample_sums_kernel's body: that kernel sits at
+// 108-124 of the 128 VGPRs its 4 waves per SIMD allow, and its allocation moved with every form
+// tried -- moving its unchanged body into a __forceinline__ function alone took the bf16 kernels
+// from 108 to 114 VGPRs and the float ones from 120 to 128. Its text therefore stays as it was,
+// and the sampling below is a copy of it: the same draws, slots, meta and counts.
+//
+// A row's 32 column lanes take the columns in passes of kNsSumK (lane l: columns c0 + 4 l ..
+// c0 + 4 l + 3 of pass c0), each pass the equal-width kernel's loop with its rows in flight: a
+// 256-wide table costs a second pass, not a second float4 per row in flight (11 rows of two
+// float4 are 88 VGPRs of loads beside twice the accumulators, past the 128 the occupancy allows;
+// 5 rows of two hide the latency of no more loads than 11 of one). An entry of type t is
+// loaded in pass c0 by the lanes with c0 + 4 l < K_t; the others sit the load out (no memory
+// traffic) and add zeros to an accumulator that is never stored. Per (row, type, column) the
+// additions run in the equal-width order, so all K_t = 128 gives that kernel's bits.
+struct NsSumWidths {               // a byte per type (the launch is near its scalar registers' end)
+    uint32_t kq;                   // K_t / 4 (0 past the last type)
+    uint32_t cq;                   // (sum_{u<t} K_u) / 4
+    int sk, km;                    // sum K_t, max K_t
+};
+
+// type t's width / first column from its packed word (a shift, as the pair word's relation)
+__device__ __forceinline__ int ns_byte4(uint32_t w, int t) { return int((w >> (8 * t)) & 0xFFu) * 4; }
+
+// v, held in a vector register from here on: the launch is at the end of its scalar registers
+// (every pointer and count of NsSumArgs stays live over the row loop), and a scalar spilled to a
+// vector lane still reserves scratch for the kernel. For values the vector unit consumes anyway
+__device__ __forceinline__ uint32_t ns_in_vgpr(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// rows in flight per lane: the width, the predicate and the pass counter cost the float
+// kernels the registers of some of the 11 (ns_sum_un); 21 entries (fan-out 20) are three rounds
+// at any count from 7 to 10
+#ifndef REGNN_NS_SUM_KT_UN
+#define REGNN_NS_SUM_KT_UN 7
+#endif
+template <int G, typename XT>
+constexpr int ns_sum_kt_un() {
+    return sizeof(XT) == 2 ? ns_sum_un<G, XT>() : REGNN_NS_SUM_KT_UN;
+}
+
+template <int G, int NT, bool DERIVE, typename XT>
+__global__ void __launch_bounds__(64 * kNsSumWaves, kNsSumOcc)
+ns_sample_sums_kt_kernel(NsSumArgs A, NsSumWidths W) {
+    if (int(blockIdx.x) < A.csc_blocks) {      // the earlier hop's index ranks, as above
+        csc_rank_slot(A.csc.gsrc, A.csc.g2l, A.csc.blk_idx, A.csc.csc_cnt, A.csc.csc_rank,
+                      A.csc.cap_e, blockIdx.x * (64 * kNsSumWaves) + threadIdx.x);
+        return;
+    }
+    const int bid = blockIdx.x - A.csc_blocks, nbk = gridDim.x - A.csc_blocks;
+    constexpr int K = kNsSumK;
+    constexpr int UN = ns_sum_kt_un<G, XT>();
+    constexpr int TPW = 64 / G;                // rows per wave
+    constexpr int H = G == 64 ? 2 : 1;         // lane groups of 32 per row (each a float4 column)
+    __shared__ int wsum[kNsSumWaves * TPW];
+    const int wl = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = wl % G, tl = wv * TPW + wl / G;
+    const uint64_t gmask = G == 64 ? ~0ull : (0xFFFFFFFFull << (wl & 32));
+    const int n = A.sizes[A.hop];
+    const int k = A.k, S = k + 1;
+    const uint32_t kq = ns_in_vgpr(W.kq), cq = ns_in_vgpr(W.cq);
+    uint32_t pair[4] = {0, 0, 0, 0};
+    if constexpr (DERIVE) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pair[q] = ns_in_vgpr(A.pair[q]);
+    }
+    int etot = 0;                              // this lane's rows' edges (lane 0 of a row)
+    for (int ib = bid * (kNsSumWaves * TPW); ib < A.cap; ib += nbk * (kNsSumWaves * TPW)) {
+    const int i = ib + tl;
+    const int64_t base = int64_t(i) * S;
+    int cnt = -1;                              // -1: no row (past the batch)
+    if (i < A.cap && i >= n) {
+        if (lane == 0) {
+            A.scnt[i] = 0;
+            A.inv[i] = 1.f;
+        }
+    } else if (i < n) {
+        // ---- the sampling: ns_sample_sums_kernel's, statement by statement
+        const uint64_t seed = ns_hop_seed(A.state, A.hop);
+        const int t = A.n_id[i];
+        const int b = A.ptr[t], d = A.ptr[t + 1] - b;
+        cnt = d < k ? d : k;
+        int slot = lane < d ? lane : -1, rank = lane;  // deg <= k: every position, in order
+        int src = lane;                        // the lane holding slot `lane`'s draw
+        if (d > k) {                               // Floyd (regnn_sample_fill's spec)
+            slot = -1;
+            const int jl = d - k + lane;
+            const int my_pos = lane < k ? int((uint64_t(ns_hash(seed, uint64_t(t), uint64_t(jl))) *
+                                               uint64_t(jl + 1)) >> 32) : 0;
+            for (int q = 0; q < k; ++q) {
+                const int pos = __shfl(my_pos, q, G);
+                const bool seen = (__ballot(slot == pos) & gmask) != 0;
+                if (lane == q) slot = seen ? d - k + q : pos;
+            }
+            rank = 0;
+            for (int m = 0; m < k; ++m) {
+                const int other = __shfl(slot, m, G);
+                rank += (lane < k && other < slot) ? 1 : 0;
+            }
+            for (int m = 0; m < k; ++m)            // inverse: slot j's draw
+                if (__shfl(rank, m, G) == lane) src = m;
+        }
+        int my_t = 0, my_lo = 0, my_r = 0;     // table rows < 2^31 (checked by the host)
+        const bool meta = A.blk_rel != nullptr;
+        int tt0 = 0;                           // DERIVE: the target row's type and pair word
+        uint32_t pw = 0;
+        if constexpr (DERIVE) {
+            tt0 = ns_type_of(A, t);
+            pw = pair[0];
+#pragma unroll
+            for (int q = 1; q < 4; ++q)
+                if (tt0 == q) pw = pair[q];
+        }
+        if (lane < cnt) {
+            const int p = b + slot;
+            const int u = A.idx[p];
+            const int64_t bp = base + rank;
+            int64_t lo;
+            if constexpr (DERIVE) {
+                my_t = ns_type_of(A, u);
+                my_lo = u - ns_type_first(A, my_t);
+                my_r = int((pw >> (8 * my_t)) & 0xFFu);
+                lo = my_lo;
+            } else {
+                my_r = A.etype[p];
+                my_t = A.ntype[u];
+                lo = A.local[u];
+                my_lo = int(lo);
+            }
+            if (meta) {
+                A.blk_rel[bp] = uint8_t(my_r);
+                A.e_type[bp] = my_t;
+                A.e_off[bp] = lo;
+            }
+        }
+        // slot order: lane j < cnt takes slot j's entry, lane cnt the self loop
+        int st = __shfl(my_t, src, G), sr = __shfl(my_r, src, G), slo = __shfl(my_lo, src, G);
+        if (lane == cnt) {
+            const int64_t bp = base + cnt;
+            int64_t lo;
+            if constexpr (DERIVE) {
+                st = tt0;
+                slo = t - ns_type_first(A, tt0);
+                lo = slo;
+            } else {
+                st = A.ntype[t];
+                lo = A.local[t];
+                slo = int(lo);
+            }
+            sr = A.n_et + st;
+            if (meta) {
+                A.blk_rel[bp] = uint8_t(sr);
+                A.e_type[bp] = st;
+                A.e_off[bp] = lo;
+            }
+        }
+        if (lane == 0) {
+            A.scnt[i] = cnt;
+            A.inv[i] = 1.f / float(cnt + 1);
+        }
+        // ---- the row's input sums, a pass per K columns: entries j = h, h + H, ..
+        const int h = lane >> 5, l = lane & 31;
+        const int ne = cnt + 1;
+        const int T = A.T;
+        for (int c0 = 0; c0 < W.km; c0 += K) {
+            const int col = c0 + 4 * l;
+            float4 racc[NT];
+            float ws[NT];
+            int rt[NT];
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt) {
+                racc[tt] = make_float4(0.f, 0.f, 0.f, 0.f);
+                ws[tt] = 0.f;
+                rt[tt] = -1;
+            }
+            float4 xs = make_float4(0.f, 0.f, 0.f, 0.f);
+            int rs = -1;
+            for (int j0 = 0; j0 < ne; j0 += H * UN) {
+                typename NsRow<XT>::V x[UN];
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int j = j0 + H * u + h;
+                    const int jj = j < ne ? j : ne - 1;  // padding: a valid row, loaded, not added
+                    const int tj = __shfl(st, jj, G);
+                    const int64_t lo = __shfl(slo, jj, G);
+                    const int kt = ns_byte4(kq, tj);
+                    x[u] = typename NsRow<XT>::V{};
+                    if (col < kt) x[u] = NsRow<XT>::load(pick_tab<NT, XT>(A, tj) + lo * kt + col);
+                }
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int j = j0 + H * u + h;
+                    const int jj = j < ne ? j : ne - 1;
+                    const int tj = __shfl(st, jj, G), rj = __shfl(sr, jj, G);
+                    if (j >= ne) continue;
+                    const auto& xv = NsRow<XT>::widen(x[u]);
+                    if (rj >= A.n_et) {            // the self loop (one per row)
+                        xs = xv;
+                        rs = rj;
+                        continue;
+                    }
+#pragma unroll
+                    for (int tt = 0; tt < NT; ++tt) {
+                        if (tt != tj) continue;
+                        ws[tt] += 1.f;
+                        rt[tt] = rj;
+                        racc[tt].x += xv.x; racc[tt].y += xv.y;
+                        racc[tt].z += xv.z; racc[tt].w += xv.w;
+                    }
+                }
+            }
+            if constexpr (H == 2) {
+                // the two halves' sums (even / odd slots): half 0's first, the same bits in both
+                auto both = [&](float v) {
+                    const float o = __shfl_xor(v, 32, 64);
+                    return h == 0 ? v + o : o + v;
+                };
+#pragma unroll
+                for (int tt = 0; tt < NT; ++tt) {
+                    racc[tt] = make_float4(both(racc[tt].x), both(racc[tt].y), both(racc[tt].z),
+                                           both(racc[tt].w));
+                    ws[tt] = both(ws[tt]);
+                    rt[tt] = max(rt[tt], __shfl_xor(rt[tt], 32, 64));
+                }
+                const int rso = __shfl_xor(rs, 32, 64);
+                const float4 xo = make_float4(__shfl_xor(xs.x, 32, 64), __shfl_xor(xs.y, 32, 64),
+                                              __shfl_xor(xs.z, 32, 64), __shfl_xor(xs.w, 32, 64));
+                if (rs < 0) {
+                    xs = xo;
+                    rs = rso;
+                }
+            }
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt)
+                if (tt < T && (H == 1 || (tt & 1) == h) && col < ns_byte4(kq, tt))
+                    *reinterpret_cast<float4*>(A.s_agg + int64_t(i) * W.sk + ns_byte4(cq, tt) +
+                                               col) = racc[tt];
+            if ((H == 1 || h == 1) && col < W.km)
+                *reinterpret_cast<float4*>(A.u_self + int64_t(i) * W.km + col) = xs;
+            if (c0 > 0) continue;              // the counts and relations: the first pass's
+            if (lane < T) {
+                float wv_ = 0.f;
+                int rv_ = -1;
+#pragma unroll
+                for (int tt = 0; tt < NT; ++tt)
+                    if (tt == lane) {
+                        wv_ = ws[tt];
+                        rv_ = rt[tt];
+                    }
+                A.s_w[int64_t(i) * T + lane] = wv_;
+                A.u_rel[int64_t(i) * (T + 1) + lane] = rv_;
+            } else if (lane == T) {
+                A.u_rel[int64_t(i) * (T + 1) + T] = rs;
+            }
+        }
+    }
+    etot += cnt + 1;                           // edges of the row, self loop included
+    }
+    if (lane == 0) wsum[tl] = etot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int e = 0;
+#pragma unroll
+        for (int q = 0; q < kNsSumWaves * TPW; ++q) e += wsum[q];
+        if (e) {
+            atomicAdd(A.sizes + 8 + A.hop, e);
+            atomicAdd(reinterpret_cast<unsigned long long*>(A.state + 5), (unsigned long long)e);
+        }
+        if (bid == 0) A.sizes[A.hop + 1] = n;
+    }
+}
+
 // Backward of the sampled block's mean aggregation y[v] = s[v] sum_e tab[rel_e] x[idx_e] + b
 // (mag/regnn_layers.py:129,142-148 through torch_scatter's mean): per target row v the scaled
 // gradient s[v] g[v] is scattered to the gathered rows with hardware float atomics (the block's
@@ -1792,15 +2071,17 @@ int regnn_ns_hop_typed_sums(const int32_t* ptr, const int32_t* idx, const uint8_
                                       n_types, K, s_agg, s_w, u_self, u_rel, csc, layout, stream);
 }
 
-int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
-                               const int32_t* ntype, int32_t num_edge_types, int32_t k,
-                               int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
-                               int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
-                               const int64_t* local, int32_t* edge_type, int64_t* edge_off,
-                               const void* const* tables, int32_t dtype, int32_t n_types,
-                               int32_t K, float* s_agg, float* s_w, float* u_self, int32_t* u_rel,
-                               const regnn_ns_csc_job* csc, const regnn_ns_type_layout* layout,
-                               hipStream_t stream) {
+// regnn_ns_hop_typed_sums_dt (widths NULL: every table K wide) and _kt (one width per type) after
+// their own first checks: the shared refusals, the arguments and the launch
+static int ns_typed_sums_call(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                              const int32_t* ntype, int32_t num_edge_types, int32_t k,
+                              int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
+                              int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
+                              const int64_t* local, int32_t* edge_type, int64_t* edge_off,
+                              const void* const* tables, int32_t dtype, int32_t n_types,
+                              int32_t K, const int32_t* widths, float* s_agg, float* s_w,
+                              float* u_self, int32_t* u_rel, const regnn_ns_csc_job* csc,
+                              const regnn_ns_type_layout* layout, hipStream_t stream) {
     if (dtype != REGNN_F32 && dtype != REGNN_BF16) return REGNN_EINVAL;
     if (!ptr || !idx || !state || !sizes || !n_id || !scnt || !inv || !tables || !s_agg ||
         !s_w || !u_self || !u_rel || cap_dst <= 0 || hop < 0 || hop > 6 || num_edge_types < 0)
@@ -1827,8 +2108,17 @@ int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uin
         if (layout->type_off[n_types] >= INT32_MAX) return REGNN_EUNSUPPORTED;   // int32 node ids
         for (int t = 1; t < n_types; ++t) toff[t] = int(layout->type_off[t]);
     }
-    if (K != kNsSumK || n_types < 1 || n_types > 4 || k < 1 || k > 63) return REGNN_EUNSUPPORTED;
+    if ((!widths && K != kNsSumK) || n_types < 1 || n_types > 4 || k < 1 || k > 63)
+        return REGNN_EUNSUPPORTED;
     if (int64_t(cap_dst) * (k + 1) >= (int64_t(1) << 31)) return REGNN_EUNSUPPORTED;
+    NsSumWidths W{};
+    for (int t = 0; widths && t < n_types; ++t) {
+        if (widths[t] != 64 && widths[t] != 128 && widths[t] != 256) return REGNN_EUNSUPPORTED;
+        W.kq |= uint32_t(widths[t] / 4) << (8 * t);
+        W.cq |= uint32_t(W.sk / 4) << (8 * t);
+        W.sk += widths[t];
+        W.km = std::max(W.km, int(widths[t]));
+    }
     NsSumArgs A{};
     A.ptr = ptr; A.idx = idx; A.etype = etype; A.ntype = ntype; A.local = local;
     A.n_et = num_edge_types; A.n_id = n_id; A.sizes = sizes; A.hop = hop; A.cap = cap_dst;
@@ -1890,27 +2180,63 @@ int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uin
     };
     const bool derive = layout != nullptr;
     // a kernel per storage type (a runtime dtype would cost the float kernels registers)
-#define NS_SUMS_LAUNCH(XT)                                                                     \
+    // (and per width policy: the equal-width kernels carry no widths)
+#define NS_SUMS_LAUNCH(KERNEL, XT, ...)                                                        \
     if (k + 1 <= 32 && derive)         /* two rows per wave (32 lanes each): slot order */      \
-        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, true, XT>), grid(2 * kNsSumWaves),    \
-                           dim3(64 * kNsSumWaves), 0, stream, A);                              \
+        hipLaunchKernelGGL((KERNEL<32, 4, true, XT>), grid(2 * kNsSumWaves),                   \
+                           dim3(64 * kNsSumWaves), 0, stream, __VA_ARGS__);                    \
     else if (k + 1 <= 32)                                                                      \
-        hipLaunchKernelGGL((ns_sample_sums_kernel<32, 4, false, XT>), grid(2 * kNsSumWaves),   \
-                           dim3(64 * kNsSumWaves), 0, stream, A);                              \
+        hipLaunchKernelGGL((KERNEL<32, 4, false, XT>), grid(2 * kNsSumWaves),                  \
+                           dim3(64 * kNsSumWaves), 0, stream, __VA_ARGS__);                    \
     else if (derive)                                                                           \
-        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, true, XT>), grid(kNsSumWaves),        \
-                           dim3(64 * kNsSumWaves), 0, stream, A);                              \
+        hipLaunchKernelGGL((KERNEL<64, 4, true, XT>), grid(kNsSumWaves),                       \
+                           dim3(64 * kNsSumWaves), 0, stream, __VA_ARGS__);                    \
     else                                                                                       \
-        hipLaunchKernelGGL((ns_sample_sums_kernel<64, 4, false, XT>), grid(kNsSumWaves),       \
-                           dim3(64 * kNsSumWaves), 0, stream, A);
-    if (dtype == REGNN_BF16) {
-        NS_SUMS_LAUNCH(bf16_t)
+        hipLaunchKernelGGL((KERNEL<64, 4, false, XT>), grid(kNsSumWaves),                      \
+                           dim3(64 * kNsSumWaves), 0, stream, __VA_ARGS__);
+    if (widths && dtype == REGNN_BF16) {
+        NS_SUMS_LAUNCH(ns_sample_sums_kt_kernel, bf16_t, A, W)
+    } else if (widths) {
+        NS_SUMS_LAUNCH(ns_sample_sums_kt_kernel, float, A, W)
+    } else if (dtype == REGNN_BF16) {
+        NS_SUMS_LAUNCH(ns_sample_sums_kernel, bf16_t, A)
     } else {
-        NS_SUMS_LAUNCH(float)
+        NS_SUMS_LAUNCH(ns_sample_sums_kernel, float, A)
     }
 #undef NS_SUMS_LAUNCH
     REGNN_LAUNCH_CHECK();
     return REGNN_OK;
+}
+
+int regnn_ns_hop_typed_sums_dt(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                               const int32_t* ntype, int32_t num_edge_types, int32_t k,
+                               int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
+                               int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
+                               const int64_t* local, int32_t* edge_type, int64_t* edge_off,
+                               const void* const* tables, int32_t dtype, int32_t n_types,
+                               int32_t K, float* s_agg, float* s_w, float* u_self, int32_t* u_rel,
+                               const regnn_ns_csc_job* csc, const regnn_ns_type_layout* layout,
+                               hipStream_t stream) {
+    return ns_typed_sums_call(ptr, idx, etype, ntype, num_edge_types, k, hop, state, sizes, n_id,
+                              cap_dst, scnt, blk_rel, inv, local, edge_type, edge_off, tables,
+                              dtype, n_types, K, nullptr, s_agg, s_w, u_self, u_rel, csc, layout,
+                              stream);
+}
+
+int regnn_ns_hop_typed_sums_kt(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                               const int32_t* ntype, int32_t num_edge_types, int32_t k,
+                               int32_t hop, int64_t* state, int32_t* sizes, const int32_t* n_id,
+                               int32_t cap_dst, int32_t* scnt, uint8_t* blk_rel, float* inv,
+                               const int64_t* local, int32_t* edge_type, int64_t* edge_off,
+                               const void* const* tables, int32_t dtype, int32_t n_types,
+                               const int32_t* widths, float* s_agg, float* s_w, float* u_self,
+                               int32_t* u_rel, const regnn_ns_csc_job* csc,
+                               const regnn_ns_type_layout* layout, hipStream_t stream) {
+    if (!widths) return REGNN_EINVAL;
+    return ns_typed_sums_call(ptr, idx, etype, ntype, num_edge_types, k, hop, state, sizes, n_id,
+                              cap_dst, scnt, blk_rel, inv, local, edge_type, edge_off, tables,
+                              dtype, n_types, 0, widths, s_agg, s_w, u_self, u_rel, csc, layout,
+                              stream);
 }
 
 int regnn_ns_spmm_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,

@@ -396,6 +396,142 @@ slot_agg_bwd_kernel(const int32_t* __restrict__ sizes, int hop, const float* __r
     bins_store(gbins, slab, n_rel);
 }
 
+// The two slot kernels over regnn_ns_hop_typed_sums_kt's outputs: one width K_t in {64, 128, 256}
+// per type, U [cap][sum K_t] and the output's S part with type t at column sum_{u<t} K_u, x_self
+// [cap][max K_t]. A lane takes kSlotP float4 columns of every per-type sum, column 4 l of each
+// pass of kSlotK, and sits out the passes past a type's width. The widths come by value, a byte per
+// type (every type index is an unrolled one: scalar shifts). Kernels of their own (slot_agg_kernel's
+// scalar registers moved when its body became a width policy's: its text stays as it was); the
+// formulas and their order are slot_agg_kernel's / _bwd_kernel's, so all K_t = 128 gives their bits.
+constexpr int kSlotP = 2;          // 256 / kSlotK
+
+struct SlotWidths {                // a byte per type
+    uint32_t kq;                   // K_t / 4 (0 past the last type)
+    uint32_t cq;                   // (sum_{u<t} K_u) / 4
+    int sk, km;                    // sum K_t, max K_t
+    __device__ __forceinline__ int k(int t) const { return int((kq >> (8 * t)) & 0xFFu) * 4; }
+    __device__ __forceinline__ int col(int t) const { return int((cq >> (8 * t)) & 0xFFu) * 4; }
+};
+
+__device__ __forceinline__ float4 slot_load(bool on, const float* p) {
+    return on ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(kBlock)
+slot_agg_kt_kernel(const int32_t* __restrict__ sizes, int hop, const float* __restrict__ U,
+                   const float* __restrict__ cnt, const float* __restrict__ xself,
+                   const int32_t* __restrict__ urel, const float* __restrict__ tab, SlotWidths W,
+                   int n_et, int T, int Tp, int64_t cap, float* __restrict__ out, int64_t ld) {
+    const int n = sizes[hop];
+    const int64_t lim = min(cap, (int64_t(n) + 127) / 128 * 128);
+    const int l = threadIdx.x & 31;
+    for (int64_t v = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / 32; v < lim;
+         v += int64_t(gridDim.x) * (kBlock / 32)) {
+        float* o = out + v * ld;
+        if (v >= n) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int p = 0; p < kSlotP; ++p)
+                    if (t < T && p * kSlotK + 4 * l < W.k(t))
+                        *reinterpret_cast<float4*>(o + W.col(t) + p * kSlotK + 4 * l) =
+                            make_float4(0.f, 0.f, 0.f, 0.f);
+            if (l < Tp) o[W.sk + l] = 0.f;
+            continue;
+        }
+        const int32_t* ur = urel + v * (T + 1);
+        const int rs = ur[T], ts = rs >= 0 ? rs - n_et : -1;
+        const float ws = rs >= 0 ? tab[rs] : 0.f;
+        float4 xs[kSlotP];
+#pragma unroll
+        for (int p = 0; p < kSlotP; ++p)
+            xs[p] = slot_load(p * kSlotK + 4 * l < W.km, xself + v * W.km + p * kSlotK + 4 * l);
+        float wl = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (t >= T) continue;
+            const int r = ur[t];
+            const float wr = r >= 0 ? tab[r] : 0.f, wst = t == ts ? ws : 0.f;
+#pragma unroll
+            for (int p = 0; p < kSlotP; ++p) {
+                const int c = p * kSlotK + 4 * l;
+                if (c >= W.k(t)) continue;
+                const float4 u = *reinterpret_cast<const float4*>(U + v * W.sk + W.col(t) + c);
+                *reinterpret_cast<float4*>(o + W.col(t) + c) =
+                    make_float4(fmaf(wst, xs[p].x, wr * u.x), fmaf(wst, xs[p].y, wr * u.y),
+                                fmaf(wst, xs[p].z, wr * u.z), fmaf(wst, xs[p].w, wr * u.w));
+            }
+            if (l == t) wl = fmaf(wr, cnt[v * T + t], wst);
+        }
+        if (l < Tp) o[W.sk + l] = l < T ? wl : 0.f;
+    }
+}
+
+// <a, b> over a lane's float4 columns. The first pass's four products are fused in the orders the
+// compiler chose in slot_agg_bwd_kernel, read from its code: x first for <U, gS>, y first for
+// <x_self, gS> (as typed_agg_bwd_rows' dot). Written out, so all K_t = 128 gives that kernel's bits
+// whatever the compiler would choose here; the later passes' products are added after them
+template <bool YFIRST>
+__device__ __forceinline__ float slot_dot4(const float4& a, const float4& b) {
+    const float d = YFIRST ? fmaf(a.x, b.x, a.y * b.y) : fmaf(a.y, b.y, a.x * b.x);
+    return fmaf(a.w, b.w, fmaf(a.z, b.z, d));
+}
+
+template <bool YFIRST>
+__device__ __forceinline__ float slot_dot(const float4 (&a)[kSlotP], const float4 (&b)[kSlotP]) {
+    float d = slot_dot4<YFIRST>(a[0], b[0]);
+#pragma unroll
+    for (int p = 1; p < kSlotP; ++p) d += slot_dot4<YFIRST>(a[p], b[p]);
+    return d;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(kBlock)
+slot_agg_kt_bwd_kernel(const int32_t* __restrict__ sizes, int hop, const float* __restrict__ U,
+                       const float* __restrict__ cnt, const float* __restrict__ xself,
+                       const int32_t* __restrict__ urel, const float* __restrict__ g, int64_t ld,
+                       SlotWidths W, int n_et, int T, float* __restrict__ slab, int n_rel) {
+    constexpr int NG = kBlock / 32;
+    __shared__ float gbins[NG][256];
+    bins_zero(gbins);
+    const int n = sizes[hop];
+    const int l = threadIdx.x & 31, grp = threadIdx.x / 32;
+    float* bins = gbins[grp];
+    for (int64_t v = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / 32; v < n;
+         v += int64_t(gridDim.x) * NG) {
+        const int32_t* ur = urel + v * (T + 1);
+        const int rs = ur[T], ts = rs >= 0 ? rs - n_et : -1;
+        const float* gr = g + v * ld;
+        float4 xs[kSlotP];
+#pragma unroll
+        for (int p = 0; p < kSlotP; ++p)
+            xs[p] = slot_load(p * kSlotK + 4 * l < W.km, xself + v * W.km + p * kSlotK + 4 * l);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (t >= T) continue;
+            const int r = ur[t];
+            float4 gs[kSlotP], u[kSlotP];
+#pragma unroll
+            for (int p = 0; p < kSlotP; ++p) {
+                const int c = p * kSlotK + 4 * l;
+                gs[p] = slot_load(c < W.k(t), gr + W.col(t) + c);
+                u[p] = slot_load(c < W.k(t), U + v * W.sk + W.col(t) + c);
+            }
+            const float gw = gr[W.sk + t];
+            if (r >= 0) {
+                const float d = group_sum<32>(slot_dot<false>(u, gs));
+                if (l == 0) bins[r] += fmaf(cnt[v * T + t], gw, d);
+            }
+            if (t == ts) {
+                const float d = group_sum<32>(slot_dot<true>(xs, gs));
+                if (l == 0) bins[rs] += d + gw;
+            }
+        }
+    }
+    bins_store(gbins, slab, n_rel);
+}
+
 // ---- the mean aggregation of a block in the strided layout (regnn_ns_hop strided = 1) --------
 // row i's edges at slots [i S, i S + cnt[i]] (sampled ones in CSR order, the self loop last), the
 // slot order the CSR layout keeps: y[i] = inv[i] sum_e tab[rel_e] x[idx_e] + bias for live rows
@@ -647,43 +783,107 @@ int regnn_ns_spmm_strided_fwd(const int32_t* live, const int32_t* cnt, int32_t s
     return REGNN_EUNSUPPORTED;
 }
 
-int regnn_ns_slot_agg(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
-                      const float* x_self, const int32_t* u_rel, const float* rel_table,
-                      int32_t n_et, int32_t n_types, int32_t K, int64_t cap, float* out,
-                      int64_t ld, hipStream_t stream) {
+// What the slot entries share: K for every type (widths NULL; K = kSlotK and <= 4 types or
+// REGNN_EUNSUPPORTED) or one width per type, each 64 / 128 / 256 (the _kt entries)
+static int slot_widths(int32_t n_types, int32_t K, const int32_t* widths, SlotWidths& W) {
+    W = SlotWidths{};
+    if ((!widths && K != kSlotK) || n_types > 4) return REGNN_EUNSUPPORTED;
+    for (int t = 0; t < n_types; ++t) {
+        const int k = widths ? widths[t] : K;
+        if (k != 64 && k != 128 && k != 256) return REGNN_EUNSUPPORTED;
+        W.kq |= uint32_t(k / 4) << (8 * t);
+        W.cq |= uint32_t(W.sk / 4) << (8 * t);
+        W.sk += k;
+        W.km = std::max(W.km, k);
+    }
+    return REGNN_OK;
+}
+
+static int slot_agg_call(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                         const float* x_self, const int32_t* u_rel, const float* rel_table,
+                         int32_t n_et, int32_t n_types, int32_t K, const int32_t* widths,
+                         int64_t cap, float* out, int64_t ld, hipStream_t stream) {
     if (!sizes || !U || !cnt || !x_self || !u_rel || !rel_table || !out || hop < 0 || hop > 7 ||
         n_et < 0 || n_types < 1 || cap < 0)
         return REGNN_EINVAL;
-    if (K != kSlotK || n_types > 4) return REGNN_EUNSUPPORTED;
+    SlotWidths W;
+    if (int rc = slot_widths(n_types, K, widths, W)) return rc;
     const int Tp = (n_types + 3) & ~3;
-    if (ld < int64_t(n_types) * K + Tp || ld % 4 || reinterpret_cast<uintptr_t>(out) % 16 ||
+    if (ld < int64_t(W.sk) + Tp || ld % 4 || reinterpret_cast<uintptr_t>(out) % 16 ||
         reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(x_self) % 16)
         return REGNN_EINVAL;
     if (cap == 0) return REGNN_OK;
     int64_t grid = (cap + kBlock / 32 - 1) / (kBlock / 32);
     if (grid > kMaxGrid) grid = kMaxGrid;
-    hipLaunchKernelGGL((slot_agg_kernel<4>), dim3(unsigned(grid)), dim3(kBlock), 0, stream, sizes,
-                       hop, U, cnt, x_self, u_rel, rel_table, n_et, n_types, Tp, cap, out, ld);
+    if (widths)
+        hipLaunchKernelGGL((slot_agg_kt_kernel<4>), dim3(unsigned(grid)), dim3(kBlock), 0, stream,
+                           sizes, hop, U, cnt, x_self, u_rel, rel_table, W, n_et, n_types, Tp,
+                           cap, out, ld);
+    else
+        hipLaunchKernelGGL((slot_agg_kernel<4>), dim3(unsigned(grid)), dim3(kBlock), 0, stream,
+                           sizes, hop, U, cnt, x_self, u_rel, rel_table, n_et, n_types, Tp, cap,
+                           out, ld);
     REGNN_LAUNCH_CHECK();
     return REGNN_OK;
+}
+
+static int slot_agg_bwd_call(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                             const float* x_self, const int32_t* u_rel, const float* g,
+                             int64_t ld, int32_t n_et, int32_t n_types, int32_t K,
+                             const int32_t* widths, float* slab, int32_t n_rel,
+                             int32_t slab_rows, hipStream_t stream) {
+    if (!sizes || !U || !cnt || !x_self || !u_rel || !g || !slab || hop < 0 || hop > 7 ||
+        n_et < 0 || n_types < 1 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0)
+        return REGNN_EINVAL;
+    SlotWidths W;
+    if (int rc = slot_widths(n_types, K, widths, W)) return rc;
+    if (ld < int64_t(W.sk) + n_types || ld % 4 || reinterpret_cast<uintptr_t>(g) % 16 ||
+        reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(x_self) % 16)
+        return REGNN_EINVAL;
+    if (widths)
+        hipLaunchKernelGGL((slot_agg_kt_bwd_kernel<4>), dim3(unsigned(slab_rows)), dim3(kBlock),
+                           0, stream, sizes, hop, U, cnt, x_self, u_rel, g, ld, W, n_et, n_types,
+                           slab, n_rel);
+    else
+        hipLaunchKernelGGL((slot_agg_bwd_kernel<4>), dim3(unsigned(slab_rows)), dim3(kBlock), 0,
+                           stream, sizes, hop, U, cnt, x_self, u_rel, g, ld, n_et, n_types, slab,
+                           n_rel);
+    REGNN_LAUNCH_CHECK();
+    return REGNN_OK;
+}
+
+int regnn_ns_slot_agg(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                      const float* x_self, const int32_t* u_rel, const float* rel_table,
+                      int32_t n_et, int32_t n_types, int32_t K, int64_t cap, float* out,
+                      int64_t ld, hipStream_t stream) {
+    return slot_agg_call(sizes, hop, U, cnt, x_self, u_rel, rel_table, n_et, n_types, K, nullptr,
+                         cap, out, ld, stream);
 }
 
 int regnn_ns_slot_agg_bwd(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
                           const float* x_self, const int32_t* u_rel, const float* g, int64_t ld,
                           int32_t n_et, int32_t n_types, int32_t K, float* slab, int32_t n_rel,
                           int32_t slab_rows, hipStream_t stream) {
-    if (!sizes || !U || !cnt || !x_self || !u_rel || !g || !slab || hop < 0 || hop > 7 ||
-        n_et < 0 || n_types < 1 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0)
-        return REGNN_EINVAL;
-    if (K != kSlotK || n_types > 4) return REGNN_EUNSUPPORTED;
-    if (ld < int64_t(n_types) * K + n_types || ld % 4 || reinterpret_cast<uintptr_t>(g) % 16 ||
-        reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(x_self) % 16)
-        return REGNN_EINVAL;
-    hipLaunchKernelGGL((slot_agg_bwd_kernel<4>), dim3(unsigned(slab_rows)), dim3(kBlock), 0,
-                       stream, sizes, hop, U, cnt, x_self, u_rel, g, ld, n_et, n_types, slab,
-                       n_rel);
-    REGNN_LAUNCH_CHECK();
-    return REGNN_OK;
+    return slot_agg_bwd_call(sizes, hop, U, cnt, x_self, u_rel, g, ld, n_et, n_types, K, nullptr,
+                             slab, n_rel, slab_rows, stream);
+}
+
+int regnn_ns_slot_agg_kt(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                         const float* x_self, const int32_t* u_rel, const float* rel_table,
+                         int32_t n_et, int32_t n_types, const int32_t* widths, int64_t cap,
+                         float* out, int64_t ld, hipStream_t stream) {
+    if (!widths) return REGNN_EINVAL;
+    return slot_agg_call(sizes, hop, U, cnt, x_self, u_rel, rel_table, n_et, n_types, 0, widths,
+                         cap, out, ld, stream);
+}
+
+int regnn_ns_slot_agg_bwd_kt(const int32_t* sizes, int32_t hop, const float* U, const float* cnt,
+                             const float* x_self, const int32_t* u_rel, const float* g,
+                             int64_t ld, int32_t n_et, int32_t n_types, const int32_t* widths,
+                             float* slab, int32_t n_rel, int32_t slab_rows, hipStream_t stream) {
+    if (!widths) return REGNN_EINVAL;
+    return slot_agg_bwd_call(sizes, hop, U, cnt, x_self, u_rel, g, ld, n_et, n_types, 0, widths,
+                             slab, n_rel, slab_rows, stream);
 }
 
 }  // extern "C"

@@ -166,6 +166,13 @@ _SIG = {
     "regnn_typed_linear_fwd_kt": ([P, P, P, I64, I32, P, P, P, P, I32, P, P], ctypes.c_int),
     "regnn_typed_linear_wgrad_kt": ([P, P, P, I64, I32, P, P, I32, P, I32, P, P, P, P, P],
                                     ctypes.c_int),
+    # the sampler's sums launch and its layer-0 consumer at one width per type (widths: a host
+    # int32 array in K's place)
+    "regnn_ns_hop_typed_sums_kt": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P,
+                                    I32, I32, P, P, P, P, P, P, P, P], ctypes.c_int),
+    "regnn_ns_slot_agg_kt": ([P, I32, P, P, P, P, P, I32, I32, P, I64, P, I64, P], ctypes.c_int),
+    "regnn_ns_slot_agg_bwd_kt": ([P, I32, P, P, P, P, P, I64, I32, I32, P, P, I32, I32, P],
+                                 ctypes.c_int),
 }
 
 for _name, (_args, _ret) in _SIG.items():

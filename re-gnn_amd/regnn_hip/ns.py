@@ -226,14 +226,17 @@ class DeviceSampler:
                 skip = (lay is not None and ts.get("meta_unread", False) and mode != "on" and
                         (mode == "off" or torch.cuda.is_current_stream_capturing()))
                 rel, et, eo = (None, None, None) if skip else (blk.rel, *self.edge_meta[h])
+                # one width per type (ts["widths"], a host int32 array): the _kt entry
+                wd = ts.get("widths")
                 with timed("ns_typed_sums"):
                     # the tables' storage type (ts["dtype"]: fp32 unless the x_dict is bf16)
-                    L.call("regnn_ns_hop_typed_sums_dt", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
+                    L.call("regnn_ns_hop_typed_sums_dt" if wd is None else
+                           "regnn_ns_hop_typed_sums_kt", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
                            L.ptr(self.etype_csr), L.ptr(self.ntype), self.num_edge_types, k, h,
                            L.ptr(self.state), L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h],
                            L.ptr(b["scnt"]), L.ptr(rel), L.ptr(blk.inv), L.ptr(self.local),
                            L.ptr(et), L.ptr(eo), ts["tables"], ts.get("dtype", L.F32_CODE),
-                           ts["T"], ts["K"],
+                           ts["T"], ts["K"] if wd is None else wd,
                            L.ptr(ts["s_agg"]), L.ptr(ts["s_w"]), L.ptr(ts["u_self"]),
                            L.ptr(ts["u_rel"]),
                            ctypes.addressof(self._csc_job(h - 1)) if deferred == h - 1 else None,
@@ -1407,7 +1410,8 @@ class NSTrainer:
     def _module_bf16_unsupported(self, s):
         """why the module path cannot train on this trainer's bf16 input tables (None: it can):
         layer 0 must read the sampler's per-type input sums (_module_pre_sums) and nothing else
-        may read the raw rows."""
+        may read the raw rows. The sums launch takes <= 4 tables of width 128, or with
+        ops.NS_SUMS_KT "on" of one width per type, each 64 / 128 / 256."""
         m = self.model
         if getattr(m, "feats_type", 3) == 2:
             return "feats_type 2 (tables that learn) takes fp32 tables only"
@@ -1423,8 +1427,13 @@ class NSTrainer:
             return "x_dict keys must be the node types 0..T-1"
         if any(t.dtype != torch.bfloat16 for t in tabs):
             return "the tables must share one dtype"
-        if len(tabs) > 4 or any(t.dim() != 2 or t.shape[1] != 128 for t in tabs):
-            return "bf16 tables need width K = 128 and <= 4 node types"
+        from . import ops as _ops
+        wide = (128,) if not _ops.ns_sums_kt_on() else (64, 128, 256)
+        if len(tabs) > 4 or any(t.dim() != 2 or t.shape[1] not in wide for t in tabs):
+            if wide == (128,):
+                return ("bf16 tables need width K = 128 and <= 4 node types (a width of 64 / "
+                        "128 / 256 per type with REGNN_NS_SUMS_KT=on / ops.NS_SUMS_KT)")
+            return "bf16 tables need widths of 64 / 128 / 256 and <= 4 node types"
         if not getattr(m, "typed_first_layer_ok", lambda _x: False)(self.x_dict):
             return "the typed first layer does not apply (contiguous 16-byte aligned device tables)"
         if max(s.sizes_k) > 63:
@@ -1434,32 +1443,48 @@ class NSTrainer:
         return None
 
     def _module_pre_sums(self, s, last):
-        """relation slots, 128-wide inputs, <= 4 node types: the module path's outer hop runs as
-        the sampler's sums launch (regnn_ns_hop_typed_sums, strided, on the sampler's stream) and
-        layer 0 reads the per-type sums (ops.ns_slot_agg) instead of gathering the sampled raw
-        rows on the model's stream (mag.REGNN._typed_first_layer); hop 0 stays CSR. Tables of one
-        width per type (feats_type 5's 256 / 128 / 128 / 128) do not qualify: the sums launch has
-        one K, so layer 0 gathers their rows itself (regnn_ns_typed_agg_kt)."""
+        """relation slots, <= 4 node types, inputs 128 wide -- or, with ops.NS_SUMS_KT "on", of one
+        width per type, each 64 / 128 / 256 (feats_type 5's 256 / 128 / 128 / 128): the module
+        path's outer hop runs as the sampler's sums launch (regnn_ns_hop_typed_sums_dt / _kt,
+        strided, on the sampler's stream) and layer 0 reads the per-type sums (ops.ns_slot_agg)
+        instead of gathering the sampled raw rows on the model's stream
+        (mag.REGNN._typed_first_layer); hop 0 stays CSR. With the knob "off" tables of other
+        widths do not qualify: layer 0 gathers their rows itself (regnn_ns_typed_agg_kt)."""
+        from . import ops as _ops
         tabs = getattr(self.model, "_type_tables", lambda _x: None)(self.x_dict)
         T = len(tabs) if tabs else 0
         if (MODULE_PRE_SUMS["mode"] == "off" or not tabs or T > 4 or
-                any(t is None or t.dim() != 2 or t.shape[1] != 128 or not t.is_contiguous() or
-                    t.data_ptr() % 16 for t in tabs) or max(s.sizes_k) > 63 or
-                not relation_slots_ok(s, T)):
+                any(t is None or t.dim() != 2 for t in tabs)):
             return
-        cap, K, dev = s.caps[last], 128, self.device
+        Ks = [int(t.shape[1]) for t in tabs]
+        # (an equal width of 128 keeps the equal-width entry whatever the knob says; the widths
+        # are settled before relation_slots_ok's pass over the graph's edges, as they were)
+        kt = set(Ks) != {128}
+        if kt and not (_ops.ns_sums_kt_on() and all(K in (64, 128, 256) for K in Ks)):
+            return
+        if (any(not t.is_contiguous() or t.data_ptr() % 16 for t in tabs) or
+                max(s.sizes_k) > 63 or not relation_slots_ok(s, T)):
+            return
+        cap, dev = s.caps[last], self.device
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-        U, cnt, xself = z(cap, T, K), z(cap, T), z(cap, K)
+        if kt:
+            U, cnt, xself = z(cap, sum(Ks)), z(cap, T), z(cap, max(Ks))
+        else:
+            U, cnt, xself = z(cap, T, 128), z(cap, T), z(cap, 128)
         urel = torch.full((cap, T + 1), -1, dtype=torch.int32, device=dev)
         ptrs = (ctypes.c_void_p * T)(*[t.data_ptr() for t in tabs])
         if len({t.dtype for t in tabs}) != 1:
             return
-        s.typed_sums[last] = dict(tables=ptrs, dtype=L.dtype_code(tabs[0]), T=T, K=K, s_agg=U,
+        s.typed_sums[last] = dict(tables=ptrs, dtype=L.dtype_code(tabs[0]), T=T, K=128, s_agg=U,
                                   s_w=cnt, u_self=xself,
                                   u_rel=urel, keep=tabs,
                                   # ops.ns_slot_agg and its backward read U / cnt / xself / urel
                                   # (and the block's inv) only: not the hop's per-slot meta
                                   layout=sampler_type_layout(s, T), meta_unread=True)
+        if kt:
+            # one width per type: run_hops then calls regnn_ns_hop_typed_sums_kt
+            s.typed_sums[last]["widths"] = (ctypes.c_int32 * T)(*Ks)
+            s.blocks[last].pre_widths = tuple(Ks)
         s.hop_strided[last] = True
         s.blocks[last].pre_sums = (U, cnt, xself, urel)
 

@@ -689,6 +689,11 @@ NS_GAT_BWD_ROWS = {"n": int(os.environ.get("REGNN_NS_GAT_BWD_ROWS", "1024"))}
 # zero fill, the same bits on every run (regnn_ns_gat_bwd_gather / regnn_ns_gatv2_bwd_gather)
 NS_GAT_SRC = {"mode": os.environ.get("REGNN_NS_GAT_SRC", "atomic")}
 NS_TIDX_CHUNK = 256              # include/regnn_hip.h REGNN_NS_TIDX_CHUNK
+# the sampler's sums launch at one input width per node type (feats_type 5's 256 / 128 / 128 /
+# 128; regnn_ns_hop_typed_sums_kt + regnn_ns_slot_agg_kt): "off": such tables keep layer 0's own
+# gather (regnn_ns_typed_agg_kt) and bf16 tables need an equal width of 128; "on": the module
+# path's outer hop forms their per-type sums too, fp32 or bf16 tables
+NS_SUMS_KT = {"mode": os.environ.get("REGNN_NS_SUMS_KT", "off")}
 
 
 def ns_gat_src_mode():
@@ -697,6 +702,14 @@ def ns_gat_src_mode():
     if mode not in ("atomic", "gather"):
         raise ValueError(f"REGNN_NS_GAT_SRC / ops.NS_GAT_SRC is {mode!r}: 'atomic' or 'gather'")
     return mode
+
+
+def ns_sums_kt_on():
+    """NS_SUMS_KT's mode as a bool, checked at first use"""
+    mode = NS_SUMS_KT["mode"]
+    if mode not in ("off", "on"):
+        raise ValueError(f"REGNN_NS_SUMS_KT / ops.NS_SUMS_KT is {mode!r}: 'off' or 'on'")
+    return mode == "on"
 
 
 class NsTidx:
@@ -1053,47 +1066,58 @@ class _NsSlotAgg(torch.autograd.Function):
     """[S | w | 0] of regnn_ns_typed_agg (ext) from the sampler's per-type input sums (relation
     slots; regnn_ns_slot_agg): pre = the slot's U [cap, T, K], counts [cap, T], self rows [cap, K]
     and slot relations [cap, T + 1] the outer hop's sums launch wrote; backward: the relation
-    table's gradient (regnn_ns_slot_agg_bwd + the fixed-order slab reduce)."""
+    table's gradient (regnn_ns_slot_agg_bwd + the fixed-order slab reduce). widths (one input
+    width per node type, regnn_ns_hop_typed_sums_kt's outputs): U [cap, sum K_t], self rows
+    [cap, max K_t], and the _kt entries."""
 
     @staticmethod
-    def forward(ctx, tab, blk, pre, n_et):
+    def forward(ctx, tab, blk, pre, n_et, widths):
         U, cnt, xself, urel = pre
-        cap, T, K = U.shape
-        Tp = _ext_pad(T)
-        ld = T * K + Tp
+        cap, T = cnt.shape
+        if widths is None:
+            name, SK, wd = "regnn_ns_slot_agg", T * U.shape[2], int(U.shape[2])
+        else:
+            name, SK, wd = "regnn_ns_slot_agg_kt", sum(widths), (ctypes.c_int32 * T)(*widths)
+        ld = SK + _ext_pad(T)
         out = torch.empty(cap, ld, dtype=torch.float32, device=U.device)
         t = tab.detach().float().contiguous()
         with timed("ns_slot_agg"):
-            L.call("regnn_ns_slot_agg", L.ptr(blk.live_rows), 0, L.ptr(U), L.ptr(cnt),
-                   L.ptr(xself), L.ptr(urel), L.ptr(t), int(n_et), T, K, cap, L.ptr(out), ld,
+            L.call(name, L.ptr(blk.live_rows), 0, L.ptr(U), L.ptr(cnt),
+                   L.ptr(xself), L.ptr(urel), L.ptr(t), int(n_et), T, wd, cap, L.ptr(out), ld,
                    L.stream())
-        ctx.blk, ctx.pre, ctx.n_et = blk, pre, int(n_et)
+        ctx.blk, ctx.pre, ctx.n_et, ctx.wd = blk, pre, int(n_et), wd
         ctx.n_rel, ctx.tab_shape = t.numel(), tab.shape
         return out
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
-            return None, None, None, None
+            return None, None, None, None, None
         U, cnt, xself, urel = ctx.pre
-        cap, T, K = U.shape
+        cap, T = cnt.shape
         g = g.contiguous().float()
         rows = int(min(L.slab_rows(), max(1, -(-cap // 8))))   # 8 row groups per block
         if SLOT_BWD_ROWS["n"] > 0:
             rows = min(rows, SLOT_BWD_ROWS["n"])
         slab = torch.empty(rows, ctx.n_rel, dtype=torch.float32, device=U.device)
+        kt = not isinstance(ctx.wd, int)
         with timed("ns_slot_agg_bwd"):
-            L.call("regnn_ns_slot_agg_bwd", L.ptr(ctx.blk.live_rows), 0, L.ptr(U), L.ptr(cnt),
-                   L.ptr(xself), L.ptr(urel), L.ptr(g), g.stride(0), ctx.n_et, T, K, L.ptr(slab),
-                   ctx.n_rel, rows, L.stream())
-        return _reduce(slab, ctx.n_rel).view(ctx.tab_shape), None, None, None
+            L.call("regnn_ns_slot_agg_bwd_kt" if kt else "regnn_ns_slot_agg_bwd",
+                   L.ptr(ctx.blk.live_rows), 0, L.ptr(U), L.ptr(cnt),
+                   L.ptr(xself), L.ptr(urel), L.ptr(g), g.stride(0), ctx.n_et, T, ctx.wd,
+                   L.ptr(slab), ctx.n_rel, rows, L.stream())
+        return _reduce(slab, ctx.n_rel).view(ctx.tab_shape), None, None, None, None
 
 
 def ns_slot_agg(blk, tab, n_et):
     """ns_typed_agg(..., ext=True) for a block whose sampler formed layer 0's per-type input sums
     (blk.pre_sums: relation slots, regnn_ns_hop_typed_sums): the same [S | w | 0] operand from one
-    read of contiguous sums per row; differentiable in tab."""
-    return _NsSlotAgg.apply(tab, blk, blk.pre_sums, int(n_et))
+    read of contiguous sums per row; differentiable in tab. A 2-d U (blk.pre_sums[0]: [cap, sum
+    K_t], regnn_ns_hop_typed_sums_kt's layout) goes with blk.pre_widths, the width per type."""
+    widths = None
+    if blk.pre_sums[0].dim() == 2:
+        widths = tuple(int(k) for k in blk.pre_widths)
+    return _NsSlotAgg.apply(tab, blk, blk.pre_sums, int(n_et), widths)
 
 
 _CAST_CACHE = {}
@@ -1136,7 +1160,8 @@ def typed_agg_layout_ok(tables, pre_sums=False):
     tables, each 64, 128 or 256 wide (one width per type: regnn_ns_typed_agg_kt; an equal width
     of 64 / 128: regnn_ns_typed_agg). pre_sums: layer 0 reads the sampler's per-type input sums
     (ns_slot_agg over blk.pre_sums), never the tables, which may then also all be bf16 at the
-    sums launch's shapes (regnn_ns_hop_typed_sums_dt: equal width 128, <= 4 tables)."""
+    sums launch's shapes: <= 4 tables of an equal width 128 (regnn_ns_hop_typed_sums_dt) or,
+    with NS_SUMS_KT "on", each 64 / 128 / 256 wide (regnn_ns_hop_typed_sums_kt)."""
     if not tables or len(tables) > 8 or any(t is None for t in tables):
         return False
     dt = tables[0].dtype
@@ -1144,7 +1169,9 @@ def typed_agg_layout_ok(tables, pre_sums=False):
         return False
     Ks = [int(t.shape[1]) for t in tables]
     if dt == torch.bfloat16:
-        return bool(pre_sums) and set(Ks) == {128} and len(tables) <= 4
+        if not pre_sums or len(tables) > 4:
+            return False
+        return set(Ks) == {128} or (ns_sums_kt_on() and all(K in (64, 128, 256) for K in Ks))
     return dt == torch.float32 and all(K in (64, 128, 256) for K in Ks)
 
 

@@ -21,8 +21,16 @@ JSON line: each leg's per-step median, min and max over the rounds (us), and whe
 ran the typed first layer over a meta-only last hop (module_lean).
 --kernel-steps K > 0: after the windows, K more eager steps under regnn_hip.profile's event timers;
 the device time per step of the typed layer-0 operators (ns_typed_agg, ns_typed_agg_bwd,
-typed_linear, typed_wgrad) goes into "kernel_us_per_step". A label the step never launched is
+typed_linear, typed_wgrad) and of the sampler's sums route (ns_typed_sums, ns_slot_agg,
+ns_slot_agg_bwd) goes into "kernel_us_per_step". A label the step never launched is
 absent (with the sampler's pre-sums on, equal widths never launch ns_typed_agg).
+
+--sums-kt off[,on[,on-bf16]]: the legs are captured pipelined trainers instead, one per entry, under
+ops.NS_SUMS_KT "off" / "on" / "on" with the tables stored in bf16 (the sampler's sums launch at one
+width per type); the windows alternate between them, "kernel_us_per_step" is per entry (an eager
+trainer each), and every leg reports the device memory its trainer added at its peak
+(trainer_peak_mb, on top of what was allocated before it was built; tables_mb: its input tables).
+A tree without the knob runs "--sums-kt off" only: the parent's leg of an A/B.
 """
 import argparse
 import json
@@ -51,6 +59,7 @@ def main():
     ap.add_argument("--widths", default="256,128,128,128")
     ap.add_argument("--legs", default="eager,captured")
     ap.add_argument("--kernel-steps", type=int, default=0)
+    ap.add_argument("--sums-kt", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -76,7 +85,25 @@ def main():
     y = torch.full((gd["N"], 1), -1, dtype=torch.int64, device=dev)
     y[:n_paper, 0] = torch.randint(0, 349, (n_paper,), generator=gen, device=dev)
 
-    def trainer(pipeline):
+    def knob(entry):
+        """ops.NS_SUMS_KT for a --sums-kt entry (None: left alone) and the entry's tables"""
+        if entry is None:
+            return x_dict
+        from regnn_hip import ops
+        if hasattr(ops, "NS_SUMS_KT"):
+            ops.NS_SUMS_KT["mode"] = "off" if entry == "off" else "on"
+        elif entry != "off":
+            sys.exit("ns_widths_time: this tree has no ops.NS_SUMS_KT (--sums-kt off only)")
+        return x_bf16 if entry == "on-bf16" else x_dict
+
+    entries = args.sums_kt.split(",") if args.sums_kt else []
+    if any(e not in ("off", "on", "on-bf16") for e in entries):
+        sys.exit("ns_widths_time: --sums-kt takes off, on, on-bf16")
+    x_bf16 = ({k: v.bfloat16().contiguous() for k, v in x_dict.items()}
+              if "on-bf16" in entries else None)
+
+    def trainer(pipeline, entry=None):
+        x_dict = knob(entry)
         torch.manual_seed(3)
         model = mag.REGNN(widths[0], args.hidden, 349, 2, 10.0, args.dropout,
                           dict(enumerate(widths)), 7, use_norm="ln", self_loop_type=2).to(dev)
@@ -87,14 +114,32 @@ def main():
         assert tr.fused is None
         return tr
 
-    legs, errors = {}, {}
-    tr_e = trainer(False)
-    for _ in range(args.warmup):
-        tr_e.step()
-    torch.cuda.synchronize()
-    legs["eager"] = (tr_e, lambda k: [tr_e.step() for _ in range(k)])
+    legs, errors, mem = {}, {}, {}
+    mb = lambda b: round(b / 2 ** 20, 1)          # noqa: E731
+    for e in entries:
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        tr = trainer(True, e)
+        tr.capture(warmup=2)
+        tr.run_steps(args.warmup)
+        torch.cuda.synchronize()
+        tabs = x_bf16 if e == "on-bf16" else x_dict
+        mem["kt_" + e] = {"trainer_peak_mb": mb(torch.cuda.max_memory_allocated() - base),
+                          "tables_mb": mb(sum(t.numel() * t.element_size()
+                                              for t in tabs.values())),
+                          "pre_sums": getattr(tr.slots[0].blocks[-1], "pre_sums", None)
+                          is not None}
+        legs["kt_" + e] = (tr, tr.run_steps)
+    tr_e = None
+    if not entries:
+        tr_e = trainer(False)
+        for _ in range(args.warmup):
+            tr_e.step()
+        torch.cuda.synchronize()
+        legs["eager"] = (tr_e, lambda k: [tr_e.step() for _ in range(k)])
     try:
-        if "captured" not in args.legs.split(","):
+        if "captured" not in args.legs.split(",") or entries:
             raise RuntimeError("leg not asked for (--legs)")
         tr_c = trainer(True)
         tr_c.capture(warmup=2)
@@ -103,7 +148,8 @@ def main():
         legs["captured"] = (tr_c, tr_c.run_steps)
     except Exception as e:                      # noqa: BLE001 (the step cannot be captured)
         torch.cuda.synchronize()
-        errors["captured"] = f"{type(e).__name__}: {e}".splitlines()[0][:200]
+        if not entries:
+            errors["captured"] = f"{type(e).__name__}: {e}".splitlines()[0][:200]
     us = {k: [] for k in legs}
     for _ in range(args.rounds):
         for k, (_tr, run) in legs.items():
@@ -122,19 +168,33 @@ def main():
                   "min": round(min(v), 1), "max": round(max(v), 1),
                   "final_loss": float(tr.loss),
                   "module_lean": bool(getattr(tr, "_module_lean", False))}
+        out[k].update(mem.get(k, {}))
     for k, e in errors.items():
         out[k] = {"error": e}
-    if args.kernel_steps > 0:
+    labels = ("ns_typed_agg", "ns_typed_agg_bwd", "typed_linear", "typed_wgrad", "ns_typed_sums",
+              "ns_slot_agg", "ns_slot_agg_bwd")
+
+    def kernel_us(tr):
+        """device time per step of the layer-0 operators over kernel_steps eager steps"""
         from regnn_hip import profile
         profile.enable()
         for _ in range(args.kernel_steps):
-            tr_e.step()
+            tr.step()
         torch.cuda.synchronize()
-        out["kernel_us_per_step"] = {
-            k: round(v[2] * 1e3 / args.kernel_steps, 1)
-            for k, v in sorted(profile.summary().items())
-            if k in ("ns_typed_agg", "ns_typed_agg_bwd", "typed_linear", "typed_wgrad")}
+        res = {k: round(v[2] * 1e3 / args.kernel_steps, 1)
+               for k, v in sorted(profile.summary().items()) if k in labels}
         profile.enable(False)
+        return res
+
+    if args.kernel_steps > 0 and tr_e is not None:
+        out["kernel_us_per_step"] = kernel_us(tr_e)
+    for e in entries if args.kernel_steps > 0 else []:
+        tr = trainer(False, e)
+        for _ in range(args.warmup):
+            tr.step()
+        torch.cuda.synchronize()
+        out["kt_" + e]["kernel_us_per_step"] = kernel_us(tr)
+        del tr
     line = json.dumps(out)
     print(line)
     if args.out:

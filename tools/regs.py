@@ -31,6 +31,8 @@ def main():
             m = re.search(r"\." + k + r":\s+(\d+)", b)
             return m.group(1) if m else None
         print(f"{nm.group(1)[:70]:72s} vgpr {g('vgpr_count')} agpr {g('agpr_count')} "
+              f"sgpr {g('sgpr_count')} lds {g('group_segment_fixed_size')} "
+              f"scratch {g('private_segment_fixed_size')} "
               f"sgpr-spill {g('sgpr_spill_count')} vgpr-spill {g('vgpr_spill_count')}")
 
 
