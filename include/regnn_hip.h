@@ -1557,6 +1557,44 @@ int regnn_typed_linear_wgrad_kt(const int64_t* order, const int64_t* src, const 
                                 const float* gY, float* slab, float* const* gW, float* const* gb,
                                 hipStream_t stream);
 
+/* The _kt entries that read raw input-table rows, with the tables' storage type: `tab` / `tables`
+ * is a host array of device pointers to tables of `dtype` (the argument after it), REGNN_F32 or
+ * REGNN_BF16; every other argument is the _kt entry's. REGNN_F32 forwards to the _kt entry.
+ * REGNN_BF16: tab[t] is bf16 [*, K_t[t]] (a bf16 feature table, x.bfloat16(): half the bytes), read
+ * by the same kernels with the row type a template parameter -- regnn_ns_typed_agg's lane loads its
+ * columns 4 l .. 4 l + 3 as one 8-byte vector, the Linear's LDS staging 8 bytes per 4 columns, each
+ * element widened by bits << 16 (exact), and nothing after the load differs (lane-to-column map,
+ * fmaf / MFMA order, chunk walk, slab layout, reduce): every output holds, bit for bit, what the
+ * _kt entry gives on the tables widened to fp32. Weights, biases, S / wsum, gradients and slabs stay
+ * fp32; regnn_typed_slab_floats is called as for the _kt entry. K_t covers the equal-width case
+ * (all entries equal). Refused before any launch: a dtype other than the two, a NULL or
+ * non-16-byte-aligned table (the Linear too: no zero rows for a NULL table here), a NULL K_t,
+ * T / n_types outside 1..8 and whatever the _kt entry refuses with REGNN_EINVAL: REGNN_EINVAL; a
+ * width outside {64, 128, 256}, O not a multiple of 16 (fwd) / 64 (wgrad): REGNN_EUNSUPPORTED.
+ * Added without an ABI bump (the version stays 51): new symbols only. */
+int regnn_typed_linear_fwd_dt(const int64_t* order, const int64_t* src, const int32_t* type_off,
+                              int64_t n, int32_t T, const void* const* tab, int32_t dtype,
+                              const float* const* W, const float* const* b, const int32_t* K_t,
+                              int32_t O, float* Y, hipStream_t stream);
+int regnn_typed_linear_wgrad_dt(const int64_t* order, const int64_t* src, const int32_t* type_off,
+                                int64_t n, int32_t T, const void* const* tab, int32_t dtype,
+                                const int32_t* wgroup, int32_t G, const int32_t* K_t, int32_t O,
+                                const float* gY, float* slab, float* const* gW, float* const* gb,
+                                hipStream_t stream);
+int regnn_ns_typed_agg_dt(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                          const float* rel_table, const int32_t* n_id, const int32_t* ntype,
+                          const int64_t* local, const int32_t* e_type, const int64_t* e_off,
+                          const void* const* tables, int32_t dtype, int32_t n_types,
+                          const int32_t* K_t, int64_t n_rows, float* S, float* wsum, int64_t ld_s,
+                          int64_t ld_w, hipStream_t stream);
+int regnn_ns_typed_agg_dt_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                              const int32_t* n_id, const int32_t* ntype, const int64_t* local,
+                              const int32_t* e_type, const int64_t* e_off,
+                              const void* const* tables, int32_t dtype, int32_t n_types,
+                              const int32_t* K_t, int64_t n_rows, const float* gS, const float* gw,
+                              int64_t ld_s, int64_t ld_w, float* slab, int32_t n_rel,
+                              int32_t slab_rows, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,7 +99,9 @@ struct TypeWidths {
 // S [n_rows][sum K_t] (row stride lds floats), w [n_rows][T] (row stride ldw). LPR lanes per row,
 // 64 / LPR rows per wave. Lane l keeps columns 4 l .. 4 l + 3 of every S_t, summed by fmaf in
 // entry order: the two policies give the same bits where all K_t = 4 LPR.
-template <int LPR, int NT, class WP>
+// XT: the tables' storage type (fp32, or bf16: a lane's four columns are one 8-byte load, widened
+// exactly; the sums are then those of the widened tables, bit for bit).
+template <int LPR, int NT, typename XT = float, class WP>
 __device__ __forceinline__ void
 typed_agg_rows(const WP& Wd, const int32_t* __restrict__ ptr, const EdgeSrc& E,
                const uint8_t* __restrict__ rel, const float* __restrict__ tab, const Tabs& xt,
@@ -140,7 +142,8 @@ typed_agg_rows(const WP& Wd, const int32_t* __restrict__ ptr, const EdgeSrc& E,
                     const int kq = Wd.kq(tt[u]);
                     x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (l < kq)
-                        x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
+                        x[u] = row4(reinterpret_cast<const XT*>(pick_tab<NT>(xt, tt[u])),
+                                    rw * kq + l);
                 }
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
@@ -180,13 +183,13 @@ typed_agg_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __re
                               ldw);
 }
 
-template <int KM, int NT>
+template <int KM, int NT, typename XT = float>
 __global__ void __launch_bounds__(kBlock)
 typed_agg_kt_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* __restrict__ rel,
                     const float* __restrict__ tab, Tabs xt, Widths W, int T, int64_t n_rows,
                     float* __restrict__ S, float* __restrict__ wsum, int64_t lds, int64_t ldw) {
-    typed_agg_rows<KM / 4, NT>(TypeWidths<NT>{W}, ptr, E, rel, tab, xt, T, n_rows, S, wsum, lds,
-                               ldw);
+    typed_agg_rows<KM / 4, NT, XT>(TypeWidths<NT>{W}, ptr, E, rel, tab, xt, T, n_rows, S, wsum,
+                                   lds, ldw);
 }
 
 // The relation bins of the backward kernels: one [256] row per row group in LDS, zeroed first ...
@@ -213,7 +216,7 @@ __device__ __forceinline__ void bins_store(const float (&gbins)[NG][256], float*
 // [n_rel] per block (the caller reduces the slab in a fixed order): bitwise reproducible, no float
 // atomics. The dot's butterfly runs over LPR lanes, with TypeWidths the lanes past K_t / 4 adding
 // zeros: the per-type kernel's bits are its own, not the equal-width kernel's.
-template <int LPR, int NT, class WP>
+template <int LPR, int NT, typename XT = float, class WP>
 __device__ __forceinline__ void
 typed_agg_bwd_rows(const WP& Wd, const int32_t* __restrict__ ptr, const EdgeSrc& E,
                    const uint8_t* __restrict__ rel, const Tabs& xt, int T, int64_t n_rows,
@@ -258,7 +261,8 @@ typed_agg_bwd_rows(const WP& Wd, const int32_t* __restrict__ ptr, const EdgeSrc&
                     const int kq = Wd.kq(tt[u]);
                     x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (l < kq)
-                        x[u] = reinterpret_cast<const float4*>(pick_tab<NT>(xt, tt[u]))[rw * kq + l];
+                        x[u] = row4(reinterpret_cast<const XT*>(pick_tab<NT>(xt, tt[u])),
+                                    rw * kq + l);
                 }
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
@@ -290,14 +294,14 @@ typed_agg_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E, const uint8_t* 
                                   n_rel, lds, ldw);
 }
 
-template <int KM, int NT>
+template <int KM, int NT, typename XT = float>
 __global__ void __launch_bounds__(kBlock)
 typed_agg_kt_bwd_kernel(const int32_t* __restrict__ ptr, EdgeSrc E,
                         const uint8_t* __restrict__ rel, Tabs xt, Widths W, int T, int64_t n_rows,
                         const float* __restrict__ gS, const float* __restrict__ gw,
                         float* __restrict__ slab, int n_rel, int64_t lds, int64_t ldw) {
-    typed_agg_bwd_rows<KM / 4, NT>(TypeWidths<NT>{W}, ptr, E, rel, xt, T, n_rows, gS, gw, slab,
-                                   n_rel, lds, ldw);
+    typed_agg_bwd_rows<KM / 4, NT, XT>(TypeWidths<NT>{W}, ptr, E, rel, xt, T, n_rows, gS, gw, slab,
+                                       n_rel, lds, ldw);
 }
 
 // ---- layer 0 from the sampler's per-type input sums (relation slots) -------------------------
@@ -608,25 +612,26 @@ using namespace regnn::nsagg;
 // widths, K_t[t] per type for the _kt entries (each in {64, 128, 256}: REGNN_EUNSUPPORTED
 // otherwise) or, K_t null, K for every type (any K: the launch refuses what it has no kernel for);
 // the S / gS operand `s`, 16-byte aligned, ld_s >= sum K_t and a multiple of 4, ld_w >= n_types.
+// bf: the tables hold bf16 rows (the _dt entries; per-type widths only), carried as float pointers.
 struct AggCall {
     const int32_t* ptr; EdgeSrc E; const uint8_t* rel; Tabs xt; Widths W;
-    bool per_type;
+    bool per_type, bf;
     int km, T;                 // the widest table (LPR = km / 4), node types
     int64_t n_rows, lds, ldw; hipStream_t stream;
 };
 
 static int agg_call(AggCall& c, const int32_t* ptr, const uint8_t* rel,
-                    const float* const* tables, int32_t n_types, const int32_t* K_t, int32_t K,
-                    int64_t n_rows, const float* s, int64_t ld_s, int64_t ld_w,
+                    const void* const* tables, bool bf, int32_t n_types, const int32_t* K_t,
+                    int32_t K, int64_t n_rows, const float* s, int64_t ld_s, int64_t ld_w,
                     hipStream_t stream) {
-    c.ptr = ptr, c.rel = rel, c.xt = Tabs{}, c.W = Widths{}, c.per_type = K_t != nullptr;
+    c.ptr = ptr, c.rel = rel, c.xt = Tabs{}, c.W = Widths{}, c.per_type = K_t != nullptr, c.bf = bf;
     c.km = 0, c.T = n_types, c.n_rows = n_rows, c.lds = ld_s, c.ldw = ld_w, c.stream = stream;
     int64_t sk = 0;
     for (int t = 0; t < n_types; ++t) {
         const int k = K_t ? K_t[t] : K;
         if (K_t && k != 64 && k != 128 && k != 256) return REGNN_EUNSUPPORTED;
         if (!tables[t] || reinterpret_cast<uintptr_t>(tables[t]) % 16) return REGNN_EINVAL;
-        c.xt.p[t] = tables[t];
+        c.xt.p[t] = static_cast<const float*>(tables[t]);
         c.W.kq[t] = k / 4;
         c.W.cq[t] = int(sk / 4);
         sk += k;
@@ -642,7 +647,10 @@ template <int KK, int N>
 static int agg_fwd_at(const AggCall& c, const float* tab, float* S, float* wsum) {
     const int64_t rpb = int64_t(kBlock / 64) * (64 / (KK / 4));
     const dim3 grid(unsigned(std::min<int64_t>((c.n_rows + rpb - 1) / rpb, kMaxGrid)));
-    if (c.per_type)
+    if (c.bf)
+        hipLaunchKernelGGL((typed_agg_kt_kernel<KK, N, bf16_t>), grid, dim3(kBlock), 0, c.stream,
+                           c.ptr, c.E, c.rel, tab, c.xt, c.W, c.T, c.n_rows, S, wsum, c.lds, c.ldw);
+    else if (c.per_type)
         hipLaunchKernelGGL((typed_agg_kt_kernel<KK, N>), grid, dim3(kBlock), 0, c.stream, c.ptr,
                            c.E, c.rel, tab, c.xt, c.W, c.T, c.n_rows, S, wsum, c.lds, c.ldw);
     else if constexpr (KK <= 128)
@@ -656,7 +664,11 @@ static int agg_fwd_at(const AggCall& c, const float* tab, float* S, float* wsum)
 template <int KK, int N>
 static int agg_bwd_at(const AggCall& c, const float* gS, const float* gw, float* slab, int n_rel,
                       int slab_rows) {
-    if (c.per_type)
+    if (c.bf)
+        hipLaunchKernelGGL((typed_agg_kt_bwd_kernel<KK, N, bf16_t>), dim3(unsigned(slab_rows)),
+                           dim3(kBlock), 0, c.stream, c.ptr, c.E, c.rel, c.xt, c.W, c.T, c.n_rows,
+                           gS, gw, slab, n_rel, c.lds, c.ldw);
+    else if (c.per_type)
         hipLaunchKernelGGL((typed_agg_kt_bwd_kernel<KK, N>), dim3(unsigned(slab_rows)),
                            dim3(kBlock), 0, c.stream, c.ptr, c.E, c.rel, c.xt, c.W, c.T, c.n_rows,
                            gS, gw, slab, n_rel, c.lds, c.ldw);
@@ -707,7 +719,8 @@ int regnn_ns_typed_agg(const int32_t* ptr, const int32_t* idx, const uint8_t* re
     if (!ptr || !rel || !rel_table || !tables || !S || !wsum || n_types <= 0 || n_types > kMT ||
         n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    int rc = agg_call(c, ptr, rel, tables, n_types, nullptr, K, n_rows, S, ld_s, ld_w, stream);
+    int rc = agg_call(c, ptr, rel, reinterpret_cast<const void* const*>(tables), false, n_types,
+                      nullptr, K, n_rows, S, ld_s, ld_w, stream);
     return rc ? rc : agg_fwd(c, rel_table, S, wsum);
 }
 
@@ -722,7 +735,8 @@ int regnn_ns_typed_agg_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t
         n_rows < 0 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0 ||
         !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    int rc = agg_call(c, ptr, rel, tables, n_types, nullptr, K, n_rows, gS, ld_s, ld_w, stream);
+    int rc = agg_call(c, ptr, rel, reinterpret_cast<const void* const*>(tables), false, n_types,
+                      nullptr, K, n_rows, gS, ld_s, ld_w, stream);
     return rc ? rc : agg_bwd(c, gS, gw, slab, n_rel, slab_rows);
 }
 
@@ -736,7 +750,8 @@ int regnn_ns_typed_agg_kt(const int32_t* ptr, const int32_t* idx, const uint8_t*
     if (!ptr || !rel || !rel_table || !tables || !K_t || !S || !wsum || n_types <= 0 ||
         n_types > kMT || n_rows < 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    int rc = agg_call(c, ptr, rel, tables, n_types, K_t, 0, n_rows, S, ld_s, ld_w, stream);
+    int rc = agg_call(c, ptr, rel, reinterpret_cast<const void* const*>(tables), false, n_types,
+                      K_t, 0, n_rows, S, ld_s, ld_w, stream);
     return rc ? rc : agg_fwd(c, rel_table, S, wsum);
 }
 
@@ -752,7 +767,50 @@ int regnn_ns_typed_agg_kt_bwd(const int32_t* ptr, const int32_t* idx, const uint
         n_types > kMT || n_rows < 0 || n_rel <= 0 || n_rel > 256 || slab_rows <= 0 ||
         !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
         return REGNN_EINVAL;
-    int rc = agg_call(c, ptr, rel, tables, n_types, K_t, 0, n_rows, gS, ld_s, ld_w, stream);
+    int rc = agg_call(c, ptr, rel, reinterpret_cast<const void* const*>(tables), false, n_types,
+                      K_t, 0, n_rows, gS, ld_s, ld_w, stream);
+    return rc ? rc : agg_bwd(c, gS, gw, slab, n_rel, slab_rows);
+}
+
+// the _kt entries with the tables' storage type: REGNN_F32 is the _kt entry itself, REGNN_BF16 its
+// kernels reading bf16 rows (every other check is the _kt entry's)
+int regnn_ns_typed_agg_dt(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                          const float* rel_table, const int32_t* n_id, const int32_t* ntype,
+                          const int64_t* local, const int32_t* e_type, const int64_t* e_off,
+                          const void* const* tables, int32_t dtype, int32_t n_types,
+                          const int32_t* K_t, int64_t n_rows, float* S, float* wsum, int64_t ld_s,
+                          int64_t ld_w, hipStream_t stream) {
+    if (dtype == REGNN_F32)
+        return regnn_ns_typed_agg_kt(ptr, idx, rel, rel_table, n_id, ntype, local, e_type, e_off,
+                                     reinterpret_cast<const float* const*>(tables), n_types, K_t,
+                                     n_rows, S, wsum, ld_s, ld_w, stream);
+    AggCall c;
+    if (dtype != REGNN_BF16 || !ptr || !rel || !rel_table || !tables || !K_t || !S || !wsum ||
+        n_types <= 0 || n_types > kMT || n_rows < 0 ||
+        !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
+        return REGNN_EINVAL;
+    int rc = agg_call(c, ptr, rel, tables, true, n_types, K_t, 0, n_rows, S, ld_s, ld_w, stream);
+    return rc ? rc : agg_fwd(c, rel_table, S, wsum);
+}
+
+int regnn_ns_typed_agg_dt_bwd(const int32_t* ptr, const int32_t* idx, const uint8_t* rel,
+                              const int32_t* n_id, const int32_t* ntype, const int64_t* local,
+                              const int32_t* e_type, const int64_t* e_off,
+                              const void* const* tables, int32_t dtype, int32_t n_types,
+                              const int32_t* K_t, int64_t n_rows, const float* gS, const float* gw,
+                              int64_t ld_s, int64_t ld_w, float* slab, int32_t n_rel,
+                              int32_t slab_rows, hipStream_t stream) {
+    if (dtype == REGNN_F32)
+        return regnn_ns_typed_agg_kt_bwd(ptr, idx, rel, n_id, ntype, local, e_type, e_off,
+                                         reinterpret_cast<const float* const*>(tables), n_types,
+                                         K_t, n_rows, gS, gw, ld_s, ld_w, slab, n_rel, slab_rows,
+                                         stream);
+    AggCall c;
+    if (dtype != REGNN_BF16 || !ptr || !rel || !tables || !K_t || !gS || !gw || !slab ||
+        n_types <= 0 || n_types > kMT || n_rows < 0 || n_rel <= 0 || n_rel > 256 ||
+        slab_rows <= 0 || !edge_src(idx, n_id, ntype, local, e_type, e_off, c.E))
+        return REGNN_EINVAL;
+    int rc = agg_call(c, ptr, rel, tables, true, n_types, K_t, 0, n_rows, gS, ld_s, ld_w, stream);
     return rc ? rc : agg_bwd(c, gS, gw, slab, n_rel, slab_rows);
 }
 

@@ -15,6 +15,8 @@
 //                   reduced in fixed chunk order (deterministic; no atomics)
 // typed_linear / typed_wgrad take one input width K for all types or one K_t per type (the _kt
 // entries): one kernel body each, the per-type form a template flag (PT), one host function each.
+// The _dt entries add the tables' storage type (XT: fp32, or bf16 rows widened as they are staged
+// into LDS -- exact, and nothing after the staging differs: the fp32 result on the widened tables).
 #include <type_traits>
 #include "regnn_common.h"
 
@@ -84,7 +86,7 @@ struct FwdArgs {
     const int64_t* src;        // [n] row of entry i in its type's table
     const int32_t* off;        // [T+1] type runs (device)
     int T, O;
-    Tabs tab;                  // [t] tables, [*, K]
+    Tabs tab;                  // [t] tables, [*, K] (of XT: bf16 tables ride as float pointers)
     Tabs W;                    // [t] weights [O, K]  (per type; may alias)
     Tabs b;                    // [t] biases [O] or NULL
     float* Y;                  // [n, O]
@@ -102,7 +104,7 @@ struct FwdKtArgs : FwdArgs {
     int kq[MT];                // K_t / 4
 };
 
-template <int KQ, int RB, bool PT>
+template <int KQ, int RB, bool PT, typename XT = float>
 __global__ void __launch_bounds__(kBlock)
 fwd_kernel(std::conditional_t<PT, FwdKtArgs, FwdArgs> A) {
     constexpr int K = 4 * KQ, LD = K + 4;
@@ -112,11 +114,11 @@ fwd_kernel(std::conditional_t<PT, FwdKtArgs, FwdArgs> A) {
     if (!chunk_of(A.off, A.T, RB, blockIdx.x, t, p0, cnt)) return;   // block-uniform
     if constexpr (PT)
         if (A.kq[t] != KQ) return;                                   // another launch's width
-    const float* tab = A.tab.p[t];
+    const XT* tab = reinterpret_cast<const XT*>(A.tab.p[t]);
     for (int e = threadIdx.x; e < RB * KQ; e += kBlock) {
         const int r = e / KQ, v = e - r * KQ;
         float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < cnt && tab) x = reinterpret_cast<const float4*>(tab + A.src[p0 + r] * K)[v];
+        if (r < cnt && tab) x = row4(tab + A.src[p0 + r] * K, v);
         *reinterpret_cast<float4*>(Xl + r * LD + 4 * v) = x;
     }
     __syncthreads();
@@ -181,7 +183,7 @@ struct WgradKtArgs : WgradArgs {
     int64_t stride;            // O * (max K_t + 1)
 };
 
-template <int KQ, bool PT>
+template <int KQ, bool PT, typename XT = float>
 __global__ void __launch_bounds__(kBlock)
 wgrad_kernel(std::conditional_t<PT, WgradKtArgs, WgradArgs> A) {
     constexpr int K = 4 * KQ, KT = K / 16, LX = K + 4, LG = 64 + 4;
@@ -196,7 +198,7 @@ wgrad_kernel(std::conditional_t<PT, WgradKtArgs, WgradArgs> A) {
         stride = A.stride;
     }
     const int og = blockIdx.y;
-    const float* tab = A.tab.p[t];
+    const XT* tab = reinterpret_cast<const XT*>(A.tab.p[t]);
     const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
     const int w = threadIdx.x >> 6;
     f32x4 acc[KT];
@@ -207,8 +209,7 @@ wgrad_kernel(std::conditional_t<PT, WgradKtArgs, WgradArgs> A) {
         for (int e = threadIdx.x; e < kWSub * KQ; e += kBlock) {
             const int r = e / KQ, v = e - r * KQ;
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r0 + r < cnt && tab)
-                x = reinterpret_cast<const float4*>(tab + A.src[p0 + r0 + r] * K)[v];
+            if (r0 + r < cnt && tab) x = row4(tab + A.src[p0 + r0 + r] * K, v);
             *reinterpret_cast<float4*>(Xl + r * LX + 4 * v) = x;
         }
         for (int e = threadIdx.x; e < kWSub * 16; e += kBlock) {
@@ -327,12 +328,13 @@ int64_t regnn_typed_slab_floats(int64_t n, int32_t T, int32_t K, int32_t O) {
     return c < 0 ? -1 : c * (int64_t)O * (K + 1);
 }
 
-// One function per pair of entries: K_t null is the equal-width entry (K for every type, PT =
-// false), else the _kt entry. One launch per distinct width present (has: 64 / 128 / 256).
+// One function per group of entries: K_t null is the equal-width entry (K for every type, PT =
+// false), else the _kt entry or, bf set, the _dt entry's bf16 tables (per-type widths only). One
+// launch per distinct width present (has: 64 / 128 / 256).
 static bool kt_width(int32_t k) { return k == 64 || k == 128 || k == 256; }
 
 static int linear_fwd(const int64_t* order, const int64_t* src, const int32_t* type_off, int64_t n,
-                      int32_t T, const float* const* tab, const float* const* W,
+                      int32_t T, const void* const* tab, bool bf, const float* const* W,
                       const float* const* b, const int32_t* K_t, int32_t K, int32_t O, float* Y,
                       hipStream_t stream) {
     if (n < 0 || T <= 0 || T > MT || !tab || !W || !b || !type_off || O <= 0 ||
@@ -346,7 +348,7 @@ static int linear_fwd(const int64_t* order, const int64_t* src, const int32_t* t
         if (!kt_width(k)) return REGNN_EUNSUPPORTED;
         if (!W[t] || !aligned16(tab[t]) || !aligned16(W[t]) || !aligned16(b[t]))
             return REGNN_EINVAL;
-        A.tab.p[t] = tab[t];
+        A.tab.p[t] = static_cast<const float*>(tab[t]);
         A.W.p[t] = W[t];
         A.b.p[t] = b[t];
         A.kq[t] = k / 4;
@@ -357,7 +359,10 @@ static int linear_fwd(const int64_t* order, const int64_t* src, const int32_t* t
     if (has[i]) {                                                                               \
         const dim3 grid(unsigned(regnn_typed_chunks(n, T, RB)));                                \
         const size_t lds = sizeof(float) * RB * (4 * KQ + 4);                                   \
-        if (K_t)                                                                                \
+        if (bf)                                                                                 \
+            hipLaunchKernelGGL((fwd_kernel<KQ, RB, true, bf16_t>), grid, dim3(kBlock), lds,     \
+                               stream, A);                                                      \
+        else if (K_t)                                                                           \
             hipLaunchKernelGGL((fwd_kernel<KQ, RB, true>), grid, dim3(kBlock), lds, stream, A); \
         else /* A's FwdArgs part */                                                             \
             hipLaunchKernelGGL((fwd_kernel<KQ, RB, false>), grid, dim3(kBlock), lds, stream, A); \
@@ -372,7 +377,8 @@ int regnn_typed_linear_fwd(const int64_t* order, const int64_t* src, const int32
                            int64_t n, int32_t T, const float* const* tab, const float* const* W,
                            const float* const* b, int32_t K, int32_t O, float* Y,
                            hipStream_t stream) {
-    return linear_fwd(order, src, type_off, n, T, tab, W, b, nullptr, K, O, Y, stream);
+    return linear_fwd(order, src, type_off, n, T, reinterpret_cast<const void* const*>(tab), false,
+                      W, b, nullptr, K, O, Y, stream);
 }
 
 int regnn_typed_linear_fwd_kt(const int64_t* order, const int64_t* src, const int32_t* type_off,
@@ -380,13 +386,37 @@ int regnn_typed_linear_fwd_kt(const int64_t* order, const int64_t* src, const in
                               const float* const* W, const float* const* b, const int32_t* K_t,
                               int32_t O, float* Y, hipStream_t stream) {
     if (!K_t) return REGNN_EINVAL;
-    return linear_fwd(order, src, type_off, n, T, tab, W, b, K_t, 0, O, Y, stream);
+    return linear_fwd(order, src, type_off, n, T, reinterpret_cast<const void* const*>(tab), false,
+                      W, b, K_t, 0, O, Y, stream);
+}
+
+// what the _dt entries refuse before the _kt checks: a dtype other than the two, no tables or
+// widths, T outside 1..8, a NULL table (the _kt Linear reads a NULL table as zero rows: not here)
+static int dt_tables(const void* const* tab, int32_t dtype, int32_t T, const int32_t* K_t) {
+    if ((dtype != REGNN_F32 && dtype != REGNN_BF16) || !tab || !K_t || T <= 0 || T > MT)
+        return REGNN_EINVAL;
+    for (int t = 0; t < T; ++t)
+        if (!tab[t] || !aligned16(tab[t])) return REGNN_EINVAL;
+    return REGNN_OK;
+}
+
+int regnn_typed_linear_fwd_dt(const int64_t* order, const int64_t* src, const int32_t* type_off,
+                              int64_t n, int32_t T, const void* const* tab, int32_t dtype,
+                              const float* const* W, const float* const* b, const int32_t* K_t,
+                              int32_t O, float* Y, hipStream_t stream) {
+    if (int rc = dt_tables(tab, dtype, T, K_t)) return rc;
+    if (dtype == REGNN_F32)
+        return regnn_typed_linear_fwd_kt(order, src, type_off, n, T,
+                                         reinterpret_cast<const float* const*>(tab), W, b, K_t, O,
+                                         Y, stream);
+    return linear_fwd(order, src, type_off, n, T, tab, true, W, b, K_t, 0, O, Y, stream);
 }
 
 static int linear_wgrad(const int64_t* order, const int64_t* src, const int32_t* type_off,
-                        int64_t n, int32_t T, const float* const* tab, const int32_t* wgroup,
-                        int32_t G, const int32_t* K_t, int32_t K, int32_t O, const float* gY,
-                        float* slab, float* const* gW, float* const* gb, hipStream_t stream) {
+                        int64_t n, int32_t T, const void* const* tab, bool bf,
+                        const int32_t* wgroup, int32_t G, const int32_t* K_t, int32_t K, int32_t O,
+                        const float* gY, float* slab, float* const* gW, float* const* gb,
+                        hipStream_t stream) {
     if (n < 0 || T <= 0 || T > MT || G <= 0 || G > T || !tab || !wgroup || !type_off ||
         !gW || !gb || !slab || (n > 0 && (!order || !src || !gY)) || !aligned16(gY))
         return REGNN_EINVAL;
@@ -404,7 +434,7 @@ static int linear_wgrad(const int64_t* order, const int64_t* src, const int32_t*
         // a weight group joins types of one width only
         if (R.gk[wgroup[t]] && R.gk[wgroup[t]] != k) return REGNN_EINVAL;
         R.gk[wgroup[t]] = k;
-        A.tab.p[t] = tab[t];
+        A.tab.p[t] = static_cast<const float*>(tab[t]);
         A.kq[t] = k / 4;
         R.wg[t] = wgroup[t];
         has[k == 64 ? 0 : k == 128 ? 1 : 2] = true;
@@ -419,7 +449,10 @@ static int linear_wgrad(const int64_t* order, const int64_t* src, const int32_t*
     const dim3 grid(unsigned(regnn_typed_chunks(n, T, kWRows)), unsigned(O / 64));
 #define TL_WGRAD(i, KQ)                                                                         \
     if (n > 0 && has[i]) {                                                                      \
-        if (K_t)                                                                                \
+        if (bf)                                                                                 \
+            hipLaunchKernelGGL((wgrad_kernel<KQ, true, bf16_t>), grid, dim3(kBlock), 0, stream, \
+                               A);                                                              \
+        else if (K_t)                                                                           \
             hipLaunchKernelGGL((wgrad_kernel<KQ, true>), grid, dim3(kBlock), 0, stream, A);     \
         else /* A's WgradArgs part */                                                           \
             hipLaunchKernelGGL((wgrad_kernel<KQ, false>), grid, dim3(kBlock), 0, stream, A);    \
@@ -439,8 +472,8 @@ int regnn_typed_linear_wgrad(const int64_t* order, const int64_t* src, const int
                              int64_t n, int32_t T, const float* const* tab, const int32_t* wgroup,
                              int32_t G, int32_t K, int32_t O, const float* gY, float* slab,
                              float* const* gW, float* const* gb, hipStream_t stream) {
-    return linear_wgrad(order, src, type_off, n, T, tab, wgroup, G, nullptr, K, O, gY, slab, gW,
-                        gb, stream);
+    return linear_wgrad(order, src, type_off, n, T, reinterpret_cast<const void* const*>(tab),
+                        false, wgroup, G, nullptr, K, O, gY, slab, gW, gb, stream);
 }
 
 int regnn_typed_linear_wgrad_kt(const int64_t* order, const int64_t* src, const int32_t* type_off,
@@ -449,8 +482,22 @@ int regnn_typed_linear_wgrad_kt(const int64_t* order, const int64_t* src, const 
                                 const float* gY, float* slab, float* const* gW, float* const* gb,
                                 hipStream_t stream) {
     if (!K_t) return REGNN_EINVAL;
-    return linear_wgrad(order, src, type_off, n, T, tab, wgroup, G, K_t, 0, O, gY, slab, gW, gb,
-                        stream);
+    return linear_wgrad(order, src, type_off, n, T, reinterpret_cast<const void* const*>(tab),
+                        false, wgroup, G, K_t, 0, O, gY, slab, gW, gb, stream);
+}
+
+int regnn_typed_linear_wgrad_dt(const int64_t* order, const int64_t* src, const int32_t* type_off,
+                                int64_t n, int32_t T, const void* const* tab, int32_t dtype,
+                                const int32_t* wgroup, int32_t G, const int32_t* K_t, int32_t O,
+                                const float* gY, float* slab, float* const* gW, float* const* gb,
+                                hipStream_t stream) {
+    if (int rc = dt_tables(tab, dtype, T, K_t)) return rc;
+    if (dtype == REGNN_F32)
+        return regnn_typed_linear_wgrad_kt(order, src, type_off, n, T,
+                                           reinterpret_cast<const float* const*>(tab), wgroup, G,
+                                           K_t, O, gY, slab, gW, gb, stream);
+    return linear_wgrad(order, src, type_off, n, T, tab, true, wgroup, G, K_t, 0, O, gY, slab, gW,
+                        gb, stream);
 }
 
 }  // extern "C"

@@ -88,6 +88,19 @@ __device__ __forceinline__ void unpack<bf16_t>(const uint4& r, float (&v)[8]) {
     }
 }
 
+// columns 4 v .. 4 v + 3 of an input-table row stored as T, as fp32: one 16-byte load, or (bf16)
+// one 8-byte load widened by bits << 16 (exact)
+template <typename T>
+__device__ __forceinline__ float4 row4(const T* row, int64_t v) {
+    if constexpr (sizeof(T) == 2) {
+        const uint2 b = reinterpret_cast<const uint2*>(row)[v];
+        return make_float4(__uint_as_float(b.x << 16), __uint_as_float(b.x & 0xffff0000u),
+                           __uint_as_float(b.y << 16), __uint_as_float(b.y & 0xffff0000u));
+    } else {
+        return reinterpret_cast<const float4*>(row)[v];
+    }
+}
+
 // Fused dropout keep mask (spec in regnn_hip.h, regnn_spmm_fwd_dropout): the murmur3 finaliser
 // over a per-call key and the element's 16-byte-vector counter, 16 bits per feature.
 __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {

@@ -173,6 +173,14 @@ _SIG = {
     "regnn_ns_slot_agg_kt": ([P, I32, P, P, P, P, P, I32, I32, P, I64, P, I64, P], ctypes.c_int),
     "regnn_ns_slot_agg_bwd_kt": ([P, I32, P, P, P, P, P, I64, I32, I32, P, P, I32, I32, P],
                                  ctypes.c_int),
+    # the row-reading _kt entries with the tables' storage type (a dtype code after the tables)
+    "regnn_typed_linear_fwd_dt": ([P, P, P, I64, I32, P, I32, P, P, P, I32, P, P], ctypes.c_int),
+    "regnn_typed_linear_wgrad_dt": ([P, P, P, I64, I32, P, I32, P, I32, P, I32, P, P, P, P, P],
+                                    ctypes.c_int),
+    "regnn_ns_typed_agg_dt": ([P, P, P, P, P, P, P, P, P, P, I32, I32, P, I64, P, P, I64, I64, P],
+                              ctypes.c_int),
+    "regnn_ns_typed_agg_dt_bwd": ([P, P, P, P, P, P, P, P, P, I32, I32, P, I64, P, P, I64, I64, P,
+                                   I32, I32, P], ctypes.c_int),
 }
 
 for _name, (_args, _ret) in _SIG.items():

@@ -464,7 +464,15 @@ class REGNN(torch.nn.Module):
         pick, or as the last resort (CPU tables, a missing type, other widths) a mask per type."""
         tabs = self._type_tables(x_dict)
         if any(torch.is_tensor(x) and x.dtype == torch.bfloat16 for x in x_dict.values()):
-            # (no upcast of a whole table here, and the gather-fused Linear reads fp32 rows)
+            # ops.BF16_ROWS "on": all-bf16 tables go through the gather-fused Linear where its
+            # shapes hold (regnn_typed_linear_fwd_dt reads the bf16 rows as they are)
+            if (ops.bf16_rows_on() and self.feats_type != 2 and tabs is not None and
+                    all(t is not None for t in tabs)):
+                Ws = [self.lins[str(k)].weight for k in range(len(tabs))]
+                bs = [self.lins[str(k)].bias for k in range(len(tabs))]
+                if ops.typed_linear_fusable(tabs, Ws, bs):
+                    return ops.typed_linear(tabs, Ws, bs, node_type, local_node_idx, n_id)
+            # (no upcast of a whole table here)
             raise ValueError("bf16 input tables are read by the NS sampler's sums launch only "
                              "(NSTrainer / FusedStep with pre_sums); group_input needs fp32 tables")
         on_dev = tabs is not None and all(t is None or (t.is_cuda and t.dtype == torch.float32
@@ -530,8 +538,11 @@ class REGNN(torch.nn.Module):
                 self.self_loop_type != 2):
             return False
         tabs = self._type_tables(x_dict)
-        # (bf16 tables: only with the sampler's input sums, which NSTrainer then insists on)
-        return (tabs is not None and ops.ns_typed_agg_ok(tabs, pre_sums=True) and
+        # (bf16 tables: only with the sampler's input sums, which NSTrainer then insists on -- or,
+        # ops.BF16_ROWS "on", wherever ops.ns_typed_agg reads them itself)
+        return (tabs is not None and
+                (ops.ns_typed_agg_ok(tabs, pre_sums=True) or
+                 (ops.BF16_ROWS["mode"] != "off" and ops.ns_typed_agg_ok(tabs))) and
                 self.convs[0].relation_weight.numel() <= 256)
 
     def _wide_epi(self, blk):
@@ -576,7 +587,8 @@ class REGNN(torch.nn.Module):
         if blk is None or getattr(blk, "inv", None) is None:
             return None
         tabs = self._type_tables(x_dict)
-        # (with blk.pre_sums the tables are never read here: they may be bf16)
+        # (with blk.pre_sums the tables are never read here: they may be bf16; without, bf16
+        # tables pass only with ops.BF16_ROWS "on" -- ops.ns_typed_agg then reads them)
         pre = getattr(blk, "pre_sums", None) is not None
         if tabs is None or not ops.ns_typed_agg_ok(tabs, pre_sums=pre) or not n_id.is_cuda:
             return None

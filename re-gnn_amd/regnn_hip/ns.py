@@ -482,7 +482,8 @@ def fused_unsupported(model, x_dict):
 def gat_blocks_unsupported(model, x_dict):
     """why NSTrainer(device_blocks=True) cannot train this model on the sampler's capacity-sized
     blocks (None: it can). Covered: mag.REGNN 'regat' (REGATConv over ops.ns_gat) with
-    self_loop_type 2 (the self loops the sampler writes), use_norm 'ln' or none, fp32 tables,
+    self_loop_type 2 (the self loops the sampler writes), use_norm 'ln' or none, fp32 tables
+    (ops.BF16_ROWS "on": or all-bf16 ones, read by group_input's gather-fused Linear),
     1..16 heads and a head width that is a multiple of 4 in [4, 512]; and, with
     mag.GATV2_BLOCKS on, 'regatv2' (REGATv2Conv over ops.ns_gatv2) under the same conditions
     and heads x head width <= 2048."""
@@ -510,8 +511,18 @@ def gat_blocks_unsupported(model, x_dict):
             return (f"{c.heads} heads x {c.out_channels}: ops.ns_gatv2 takes heads x head width "
                     f"<= {ops.NS_GATV2_MAX_WIDTH}")
     if any(torch.is_tensor(x) and x.dtype != torch.float32 for x in x_dict.values()):
-        return f"the attention path reads fp32 input tables (no bf16 tables for {kind!r})"
+        # ops.BF16_ROWS "on": group_input's gather-fused Linear reads all-bf16 tables
+        # (NSTrainer._module_bf16_unsupported then checks their shapes)
+        if not (ops.bf16_rows_on() and all(torch.is_tensor(x) and x.dtype == torch.bfloat16
+                                           for x in x_dict.values())):
+            return f"the attention path reads fp32 input tables (no bf16 tables for {kind!r})"
     return None
+
+
+def _ops_bf16_rows_on():
+    """ops.BF16_ROWS as a bool (ops is imported late throughout this module)"""
+    from . import ops
+    return ops.bf16_rows_on()
 
 
 def fused_bf16_unsupported(model, sampler, x_dict):
@@ -1301,7 +1312,8 @@ class NSTrainer:
                              getattr(model, "typed_first_layer_ok", lambda _x: False)(x_dict))
         if self.fused is None and self._blocks_ok:
             self._setup_module_slot(self.slots[0])
-        if self._bf16 and self.fused is None and \
+        # (ops.BF16_ROWS "on": without the input sums layer 0 reads the bf16 rows itself)
+        if self._bf16 and self.fused is None and not _ops_bf16_rows_on() and \
                 getattr(self.slots[0].blocks[-1], "pre_sums", None) is None:
             raise ValueError("bf16 input tables: the module path's input sums (_module_pre_sums) "
                              "did not come on")
@@ -1415,6 +1427,8 @@ class NSTrainer:
         m = self.model
         if getattr(m, "feats_type", 3) == 2:
             return "feats_type 2 (tables that learn) takes fp32 tables only"
+        if _ops_bf16_rows_on():
+            return self._bf16_rows_unsupported()
         if not self._blocks_ok:
             return "the model does not run on device blocks (regcn, self_loop_type 2)"
         if any(bool(getattr(c, "residual", False)) for c in m.convs):
@@ -1440,6 +1454,41 @@ class NSTrainer:
             return "a fan-out above 63"
         if not relation_slots_ok(s, len(tabs)):
             return "no relation slots (a type pair with several relations)"
+        return None
+
+    def _bf16_rows_unsupported(self):
+        """_module_bf16_unsupported with ops.BF16_ROWS "on" (feats_type 2 already refused): the
+        model's own readers of raw rows take all-bf16 tables -- layer 0's typed aggregation
+        (ops.ns_typed_agg, where the sampler's sums do not apply) and group_input's gather-fused
+        Linear (residual convs, the attention models, the exact-size path) -- so what remains is
+        what those kernels cannot take: <= 8 contiguous, 16-byte aligned device tables of one
+        dtype, each 64 / 128 / 256 wide, for the Linear a hidden width that is a multiple of 64."""
+        from . import ops as _ops
+        m = self.model
+        tabs = getattr(m, "_type_tables", lambda _x: None)(self.x_dict)
+        if not tabs or any(t is None for t in tabs):
+            return "x_dict keys must be the node types 0..T-1"
+        if any(t.dtype != torch.bfloat16 for t in tabs):
+            return "the tables must share one dtype"
+        Ks = [int(t.shape[1]) if t.dim() == 2 else 0 for t in tabs]
+        if len(tabs) > 8 or any(K not in (64, 128, 256) for K in Ks):
+            return (f"bf16 tables need widths of 64 / 128 / 256 and <= 8 node types (got "
+                    f"{len(tabs)} tables of widths {Ks})")
+        if not _ops.ns_typed_agg_ok(tabs):
+            return "bf16 tables must be contiguous, 16-byte aligned and on the device"
+        # group_input runs for every sampled row unless the typed first layer folds it in, and
+        # for a residual conv's target rows
+        lin = (not self._blocks_ok or self._gat_blocks or
+               any(bool(getattr(c, "residual", False)) for c in m.convs) or
+               not getattr(m, "typed_first_layer_ok", lambda _x: False)(self.x_dict))
+        if lin:
+            if getattr(m, "lins", None) is None:
+                return "the model has no per-type input Linear (mag.REGNN's lins) to read them"
+            Ws = [m.lins[str(k)].weight for k in range(len(tabs))]
+            bs = [m.lins[str(k)].bias for k in range(len(tabs))]
+            if not _ops.typed_linear_fusable(tabs, Ws, bs):
+                return (f"the gather-fused Linear (ops.typed_linear) does not take hidden width "
+                        f"{int(Ws[0].shape[0])}: a multiple of 64")
         return None
 
     def _module_pre_sums(self, s, last):

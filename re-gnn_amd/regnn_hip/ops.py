@@ -694,6 +694,11 @@ NS_TIDX_CHUNK = 256              # include/regnn_hip.h REGNN_NS_TIDX_CHUNK
 # gather (regnn_ns_typed_agg_kt) and bf16 tables need an equal width of 128; "on": the module
 # path's outer hop forms their per-type sums too, fp32 or bf16 tables
 NS_SUMS_KT = {"mode": os.environ.get("REGNN_NS_SUMS_KT", "off")}
+# bf16 input tables on the model side: "off": only the sampler's sums launch reads bf16 rows, every
+# other reader refuses them; "on": the gather-fused per-type Linear (typed_linear) and layer 0's
+# typed aggregation (ns_typed_agg) read all-bf16 tables too (the _dt entries: the fp32 result on
+# the widened tables, bit for bit), so group_input, the attention models and residual convs take them
+BF16_ROWS = {"mode": os.environ.get("REGNN_BF16_ROWS", "off")}
 
 
 def ns_gat_src_mode():
@@ -710,6 +715,19 @@ def ns_sums_kt_on():
     if mode not in ("off", "on"):
         raise ValueError(f"REGNN_NS_SUMS_KT / ops.NS_SUMS_KT is {mode!r}: 'off' or 'on'")
     return mode == "on"
+
+
+def bf16_rows_on():
+    """BF16_ROWS's mode as a bool, checked at first use"""
+    mode = BF16_ROWS["mode"]
+    if mode not in ("off", "on"):
+        raise ValueError(f"REGNN_BF16_ROWS / ops.BF16_ROWS is {mode!r}: 'off' or 'on'")
+    return mode == "on"
+
+
+def _bf16_rows(tables):
+    """True when these tables go to the _dt entries as bf16 rows (BF16_ROWS "on")"""
+    return tables[0].dtype == torch.bfloat16 and bf16_rows_on()
 
 
 class NsTidx:
@@ -991,6 +1009,10 @@ class _NsTypedAgg(torch.autograd.Function):
         # one width per type (or an equal width of 256): the _kt entries, S_t at column
         # sum_{u<t} K_u; equal widths 64 / 128 keep regnn_ns_typed_agg and its [T, K] rows
         kt = len(set(Ks)) > 1 or K == 256
+        # bf16 tables (BF16_ROWS "on"): the _dt entries, which take the width array whatever Ks
+        # (equal widths 64 / 128 keep their [T, K] rows: the same memory layout)
+        ctx.bf = bf = _bf16_rows(tables)
+        esz = tables[0].element_size()
         dev = tables[0].device
         if ext:
             # row stride sum K_t + Tp, Tp = T rounded up to 4 (the kernels take 16-byte aligned
@@ -1017,12 +1039,16 @@ class _NsTypedAgg(torch.autograd.Function):
             local_idx = _cached_cast(local_idx, torch.int64)
             e_type = e_off = None
         arr = _ptr_array([L.ptr(x) for x in tables])
-        ctx.widths = (ctypes.c_int32 * T)(*Ks) if kt else K
-        with timed("ns_typed_agg", blk.E * (4 * max(Ks) + 13) + blk.n_dst * (4 * SK + 4 * T + 8)):
-            L.call("regnn_ns_typed_agg_kt" if kt else "regnn_ns_typed_agg", L.ptr(blk.csr_ptr),
+        ctx.widths = (ctypes.c_int32 * T)(*Ks) if kt or bf else K
+        dt = (L.dtype_code(tables[0]),) if bf else ()
+        name = "regnn_ns_typed_agg_dt" if bf else \
+            "regnn_ns_typed_agg_kt" if kt else "regnn_ns_typed_agg"
+        with timed("ns_typed_agg",
+                   blk.E * (esz * max(Ks) + 13) + blk.n_dst * (4 * SK + 4 * T + 8)):
+            L.call(name, L.ptr(blk.csr_ptr),
                    L.ptr(blk.csr_idx), L.ptr(blk.rel),
                    L.ptr(t), L.ptr(n_id), L.ptr(node_type), L.ptr(local_idx), L.ptr(e_type),
-                   L.ptr(e_off), arr, T, ctx.widths, blk.n_dst, S_ptr, w_ptr, lds, ldw,
+                   L.ptr(e_off), arr, *dt, T, ctx.widths, blk.n_dst, S_ptr, w_ptr, lds, ldw,
                    L.stream())
         ctx.blk, ctx.tables, ctx.idx = blk, tables, (n_id, node_type, local_idx, e_type, e_off)
         ctx.n_rel, ctx.tab_shape, ctx.ext = t.numel(), tab.shape, bool(ext)
@@ -1051,13 +1077,17 @@ class _NsTypedAgg(torch.autograd.Function):
             gS_ptr, gw_ptr, lds, ldw = L.ptr(gS), L.ptr(gw), SK, T
         rows = L.slab_rows()
         slab = torch.empty(rows, ctx.n_rel, dtype=torch.float32, device=dev)
+        dt = (L.dtype_code(tables[0]),) if ctx.bf else ()
+        name = "regnn_ns_typed_agg_dt_bwd" if ctx.bf else \
+            "regnn_ns_typed_agg_kt_bwd" if kt else "regnn_ns_typed_agg_bwd"
         with timed("ns_typed_agg_bwd",
-                   blk.E * (4 * max(Ks) + 13) + blk.n_dst * (4 * SK + 4 * T + 8)):
-            L.call("regnn_ns_typed_agg_kt_bwd" if kt else "regnn_ns_typed_agg_bwd",
+                   blk.E * (tables[0].element_size() * max(Ks) + 13) +
+                   blk.n_dst * (4 * SK + 4 * T + 8)):
+            L.call(name,
                    L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx),
                    L.ptr(blk.rel), L.ptr(n_id), L.ptr(node_type), L.ptr(local_idx),
                    L.ptr(e_type), L.ptr(e_off),
-                   _ptr_array([L.ptr(x) for x in tables]), T, ctx.widths, blk.n_dst, gS_ptr,
+                   _ptr_array([L.ptr(x) for x in tables]), *dt, T, ctx.widths, blk.n_dst, gS_ptr,
                    gw_ptr, lds, ldw, L.ptr(slab), ctx.n_rel, rows, L.stream())
         return _reduce(slab, ctx.n_rel).view(ctx.tab_shape), None, None, None, None, None, None
 
@@ -1151,7 +1181,9 @@ def ns_typed_agg(blk, tab, n_id, tables, node_type, local_idx, ext=False):
     per-type weight sums w [n_dst, T], or with ext one [n_dst, T K + Tp] tensor [S | w | 0]
     (Tp = T rounded up to 4, zero pad columns: the projection's single GEMM operand against
     [W_c; b_c; 0]); differentiable in tab. Tables of one width per type (fp32, each 64 / 128 /
-    256): S [n_dst, sum K_t] with S_t at column sum_{u<t} K_u, ext [n_dst, sum K_t + Tp]."""
+    256): S [n_dst, sum K_t] with S_t at column sum_{u<t} K_u, ext [n_dst, sum K_t + Tp].
+    BF16_ROWS "on": all-bf16 tables too (regnn_ns_typed_agg_dt), the same shapes and, bit for
+    bit, the results of the widened tables."""
     return _NsTypedAgg.apply(tab, blk, n_id, tables, node_type, local_idx, bool(ext))
 
 
@@ -1161,7 +1193,9 @@ def typed_agg_layout_ok(tables, pre_sums=False):
     of 64 / 128: regnn_ns_typed_agg). pre_sums: layer 0 reads the sampler's per-type input sums
     (ns_slot_agg over blk.pre_sums), never the tables, which may then also all be bf16 at the
     sums launch's shapes: <= 4 tables of an equal width 128 (regnn_ns_hop_typed_sums_dt) or,
-    with NS_SUMS_KT "on", each 64 / 128 / 256 wide (regnn_ns_hop_typed_sums_kt)."""
+    with NS_SUMS_KT "on", each 64 / 128 / 256 wide (regnn_ns_hop_typed_sums_kt). Without
+    pre_sums all-bf16 tables pass only with BF16_ROWS "on", under the fp32 conditions
+    (regnn_ns_typed_agg_dt)."""
     if not tables or len(tables) > 8 or any(t is None for t in tables):
         return False
     dt = tables[0].dtype
@@ -1169,7 +1203,10 @@ def typed_agg_layout_ok(tables, pre_sums=False):
         return False
     Ks = [int(t.shape[1]) for t in tables]
     if dt == torch.bfloat16:
-        if not pre_sums or len(tables) > 4:
+        if not pre_sums:
+            # (BF16_ROWS "on": regnn_ns_typed_agg_dt reads them under the fp32 conditions)
+            return bf16_rows_on() and all(K in (64, 128, 256) for K in Ks)
+        if len(tables) > 4:
             return False
         return set(Ks) == {128} or (ns_sums_kt_on() and all(K in (64, 128, 256) for K in Ks))
     return dt == torch.float32 and all(K in (64, 128, 256) for K in Ks)
@@ -2317,13 +2354,19 @@ class _TypedLinear(torch.autograd.Function):
         Ks = [int(t.shape[1]) for t in tables]
         # one width per type: regnn_typed_linear_fwd_kt (a launch per distinct width)
         kt = len(set(Ks)) > 1
+        # bf16 tables (BF16_ROWS "on"): the _dt entries, which take the per-type width array
+        ctx.bf = bf = _bf16_rows(tables)
+        kt = kt or bf
         ctx.widths = (ctypes.c_int32 * T)(*Ks) if kt else K
+        dt = (L.dtype_code(tables[0]),) if bf else ()
+        name = "regnn_typed_linear_fwd_dt" if bf else \
+            "regnn_typed_linear_fwd_kt" if kt else "regnn_typed_linear_fwd"
         Wd = [W.detach().contiguous() for W in Ws]
         bd = [None if b is None else b.detach().contiguous() for b in bs]
-        with timed("typed_linear", n * (max(Ks) + O) * 4):
-            L.call("regnn_typed_linear_fwd_kt" if kt else "regnn_typed_linear_fwd", L.ptr(order),
+        with timed("typed_linear", n * (max(Ks) * tables[0].element_size() + O * 4)):
+            L.call(name, L.ptr(order),
                    L.ptr(src), L.ptr(off), n, T,
-                   _ptr_array([L.ptr(t) for t in tables]),
+                   _ptr_array([L.ptr(t) for t in tables]), *dt,
                    _ptr_array([L.ptr(Wd[wg[t]]) for t in range(T)]),
                    _ptr_array([L.ptr(bd[wg[t]]) for t in range(T)]), ctx.widths, O, L.ptr(Y),
                    L.stream())
@@ -2347,23 +2390,33 @@ class _TypedLinear(torch.autograd.Function):
         # (mixed widths: every chunk of the slab takes the widest type's O (K + 1) floats)
         slab = torch.empty(L.typed_slab_floats(n, T, max(ctx.gk), O), dtype=torch.float32,
                            device=dev)
-        with timed("typed_wgrad", n * (max(ctx.gk) + O) * 4):
-            L.call("regnn_typed_linear_wgrad_kt" if kt else "regnn_typed_linear_wgrad",
+        dt = (L.dtype_code(ctx.tables[0]),) if ctx.bf else ()
+        name = "regnn_typed_linear_wgrad_dt" if ctx.bf else \
+            "regnn_typed_linear_wgrad_kt" if kt else "regnn_typed_linear_wgrad"
+        with timed("typed_wgrad",
+                   n * (max(ctx.gk) * ctx.tables[0].element_size() + O * 4)):
+            L.call(name,
                    L.ptr(order), L.ptr(src), L.ptr(off), n, T,
-                   _ptr_array([L.ptr(t) for t in ctx.tables]), (ctypes.c_int32 * T)(*ctx.wg),
+                   _ptr_array([L.ptr(t) for t in ctx.tables]), *dt,
+                   (ctypes.c_int32 * T)(*ctx.wg),
                    G, ctx.widths, O, L.ptr(gY), L.ptr(slab), _ptr_array([L.ptr(x) for x in gW]),
                    _ptr_array([L.ptr(x) for x in gb]), L.stream())
         return (None, None, None, None, *gW, *gb)
 
 
 def typed_linear_fusable(tables, weights, biases):
-    """regnn_typed_linear's shapes: <= 8 types, every table fp32 contiguous [*, K_t] on the device
-    with no gradient, K_t in {64, 128, 256} (one width for all: regnn_typed_linear_fwd / _wgrad;
+    """regnn_typed_linear's shapes: <= 8 types, every table fp32 (BF16_ROWS "on": or every table
+    bf16, 16-byte aligned; the _dt entries) contiguous [*, K_t] on the device with no gradient, K_t in {64, 128, 256} (one width for all: regnn_typed_linear_fwd / _wgrad;
     one per type: the _kt entries), weights [O, K_t] with O a multiple of 64 (one per type; with
     weight groups one per group, as wide as its types' tables)."""
     if not 0 < len(tables) <= 8 or any(t is None for t in tables):
         return False
-    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+    # (BF16_ROWS "on": all-bf16 tables too, 16-byte aligned -- the _dt entries)
+    dt = tables[0].dtype
+    if dt != torch.float32 and not (dt == torch.bfloat16 and bf16_rows_on() and
+                                    all(t.data_ptr() % 16 == 0 for t in tables)):
+        return False
+    if not all(t.is_cuda and t.dtype == dt and t.dim() == 2 and t.is_contiguous()
                and not t.requires_grad for t in tables):
         return False
     Ks = [int(t.shape[1]) for t in tables]

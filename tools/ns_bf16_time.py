@@ -2,6 +2,7 @@
 
     python tools/ns_bf16_time.py [--scale 10] [--batch 512] [--steps 160] [--rounds 7]
                                  [--hidden 64|512] [--first fp32|bf16] [--only fp32|bf16]
+                                 [--residual] [--rows off|on] [--out FILE]
 
 bench.py's NS workload twice over one graph -- mag_like(scale), 128-d inputs, 349 classes, fan-out
 [25, 20], dropout 0.5, FlatAdam, pipelined and captured (NSTrainer.capture / run_steps) -- once
@@ -13,6 +14,11 @@ synchronise. Prints every round's us per step and one JSON line with each varian
 and max, the table bytes, the memory each trainer holds on top of the graph and the tables, and
 the process's peak allocated memory after capture() (--only: with that dtype's tables alone). No
 step is retried.
+
+--rows on: ops.BF16_ROWS "on" -- the model's own readers of raw rows (group_input's gather-fused
+Linear, layer 0's typed aggregation) take the bf16 tables too; --residual: residual convs (module
+path only: they project the targets' raw rows, which on bf16 tables needs --rows on). --out FILE:
+the JSON line is also written there.
 """
 import argparse
 import json
@@ -43,10 +49,14 @@ def main():
     ap.add_argument("--only", choices=["fp32", "bf16"], default=None,
                     help="build and time this variant alone (its tables only: the process's "
                          "peak allocated memory is then that of a user of this dtype)")
+    ap.add_argument("--residual", action="store_true", help="residual convs (--hidden 512)")
+    ap.add_argument("--rows", choices=["off", "on"], default="off", help="ops.BF16_ROWS")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("ns_bf16_time: needs the GPU (no CPU timing)")
-    from regnn_hip import mag, synth
+    from regnn_hip import mag, ops, synth
+    ops.BF16_ROWS["mode"] = args.rows
     from regnn_hip.graph import RelGraph
     from regnn_hip.ns import NSTrainer
     dev = "cuda"
@@ -85,7 +95,7 @@ def main():
     def trainer(x_dict):
         torch.manual_seed(3)
         model = mag.REGNN(128, args.hidden, 349, 2, 10.0, args.dropout, {k: 128 for k in x_dict},
-                          7, use_norm="ln", self_loop_type=2).to(dev)
+                          7, use_norm="ln", self_loop_type=2, residual=args.residual).to(dev)
         torch.cuda.synchronize()
         base = torch.cuda.memory_allocated()
         tr = NSTrainer(model, None, rg, [25, 20], args.batch, torch.arange(n_paper, device=dev),
@@ -117,10 +127,13 @@ def main():
             us[k].append((time.perf_counter() - t0) / args.steps * 1e6)
             print(f"round {r} {k}: {us[k][-1]:.2f} us/step", flush=True)
     engine = "fused two-layer step" if args.hidden == 64 else "module path"
+    if args.residual:
+        engine += ", residual"
     out = {"workload": f"mag_like({args.scale:g}) NS step, batch {args.batch}, fan-out [25, 20], "
                        f"hidden {args.hidden} ({engine}), dropout {args.dropout}, FlatAdam, "
                        "captured",
            "steps_per_window": args.steps, "rounds": args.rounds, "first": args.first,
+           "bf16_rows": args.rows,
            "peak_allocated_bytes_after_capture": int(peak)}
     if args.only is None:
         out["every_bf16_round_below_every_fp32_round"] = max(us["bf16"]) < min(us["fp32"])
@@ -130,7 +143,12 @@ def main():
                   "rounds_us": [round(t, 2) for t in v],
                   "table_bytes": table_bytes[k], "trainer_added_bytes": int(added[k]),
                   "final_loss": float(trs[k].loss)}
-    print(json.dumps(out))
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@ default exact-size path, in one process (bench.py times the 'regcn' step only):
 
     python tools/ns_gat_time.py [--model regat] [--scale 1] [--batch 512] [--steps 20]
                                 [--rounds 7] [--kernel-steps 0] [--src atomic] [--out FILE]
+                                [--tables fp32|bf16]
 
 One graph -- mag_like(scale), 128-d inputs, REGNN 'regat' hidden 64 x 8 heads, 349 classes,
 fan-out [25, 20], dropout 0.5, FlatAdam -- and two trainers over it:
@@ -25,6 +26,10 @@ atomics), captured as B is; the windows then alternate A, B, C, so gather is tim
 atomic form in the same process. Its peak memory is measured as B's is, and --kernel-steps times
 both forms ("kernel_us_per_step" for B, "kernel_us_per_step_gather" for C, the latter with the
 index build, ns_block_tidx, on the sampler's stream).
+
+--tables bf16: a further trainer D, path B on bf16 copies of the input tables (x.bfloat16(), with
+ops.BF16_ROWS "on": group_input's gather-fused Linear reads the bf16 rows), captured as B is and
+timed in the same alternating windows; the JSON line then carries both tables' bytes and D's peak.
 
 After warm-up runs of both, `rounds` timed windows of `steps` steps each, alternating A and B; a
 window is a host clock around the steps ending in a device synchronise. Prints (and with --out
@@ -61,6 +66,7 @@ def main():
     ap.add_argument("--kernel-steps", type=int, default=0)
     ap.add_argument("--src", choices=["atomic", "gather"], default="atomic")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--tables", choices=["fp32", "bf16"], default="fp32")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("ns_gat_time: needs the GPU (no CPU timing)")
@@ -84,7 +90,7 @@ def main():
     y = torch.full((gd["N"], 1), -1, dtype=torch.int64, device=dev)
     y[:n_paper, 0] = torch.randint(0, 349, (n_paper,), generator=gen, device=dev)
 
-    def trainer(**kw):
+    def trainer(x_dict=x_dict, **kw):
         torch.manual_seed(3)
         model = mag.REGNN(128, args.hidden, 349, 2, 10.0, args.dropout,
                           {k: 128 for k in x_dict}, 7, use_norm="ln", self_loop_type=2,
@@ -128,6 +134,21 @@ def main():
         ops.NS_GAT_SRC["mode"] = "atomic"
         runs["device_blocks_gather_captured"] = tr_c.run_steps
         trainers["device_blocks_gather_captured"] = tr_c
+    peak_d = base_d = None
+    if args.tables == "bf16":
+        xb = {k: v.bfloat16().contiguous() for k, v in x_dict.items()}
+        torch.cuda.synchronize()
+        base_d = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        ops.BF16_ROWS["mode"] = "on"
+        tr_d = trainer(x_dict=xb, device_blocks=True)
+        assert tr_d._gat_blocks and tr_d.pipelined and tr_d.ahead == 1
+        tr_d.capture(warmup=2)
+        tr_d.run_steps(args.warmup)
+        torch.cuda.synchronize()
+        peak_d = torch.cuda.max_memory_allocated()
+        runs["device_blocks_bf16_tables_captured"] = tr_d.run_steps
+        trainers["device_blocks_bf16_tables_captured"] = tr_d
     us = {k: [] for k in runs}
     for _ in range(args.rounds):
         for k, run in runs.items():
@@ -148,6 +169,12 @@ def main():
     if peak_c is not None:
         out["device_blocks_gather_peak_bytes"] = int(peak_c)
         out["allocated_before_device_blocks_gather_bytes"] = int(base_c)
+    if peak_d is not None:
+        nbytes = lambda d: sum(t.numel() * t.element_size() for t in d.values())  # noqa: E731
+        out["table_bytes"] = {"fp32": nbytes(x_dict), "bf16": nbytes(xb)}
+        # (D's peak and base both hold the fp32 tables and the earlier trainers)
+        out["device_blocks_bf16_tables_peak_bytes"] = int(peak_d)
+        out["allocated_before_device_blocks_bf16_tables_bytes"] = int(base_d)
     if args.kernel_steps > 0:
         from regnn_hip import profile
         forms = [("kernel_us_per_step", tr_b, "atomic")]
