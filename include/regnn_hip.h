@@ -615,7 +615,10 @@ int regnn_sample_fill(const int32_t* ptr, const int32_t* idx, const int32_t* tar
 int regnn_ns_labels(const int32_t* n_id, const int32_t* sizes, const int64_t* labels, int32_t B,
                     int64_t ignore, int64_t* y, hipStream_t stream);
 /* log_softmax + nll_loss over B rows of C fp32 logits z (row-major), labels y (`ignore` rows
- * skipped): forward (a wave per row, then a fixed-order sum: deterministic) writes lse[B], the
+ * skipped, and so is every row whose label lies outside [0, C) -- the -1 of an unlabelled node, as
+ * the fused step's y >= 0: regnn_softmax_xent_fwd / _bwd, regnn_ns_xent_fwd and
+ * regnn_xent_bwd_colsum never index z with such a label): forward (a wave per row, then a
+ * fixed-order sum: deterministic) writes lse[B], the
  * scratch rowloss[2 B] and out[2] = {mean loss over the valid rows, their count}; backward gz =
  * g[0] / out[1] * (softmax(z) - onehot(y)), zero rows for ignored labels (ABI 42;
  * mag/regnn_ns.py:404-405's log_softmax / nll pair). */
@@ -625,7 +628,8 @@ int regnn_softmax_xent_bwd(const float* z, const int64_t* y, const float* lse, c
                            const float* g, int32_t B, int32_t C, int64_t ignore, float* gz,
                            hipStream_t stream);
 /* The same loss for a capacity-sized sampled batch in one launch (ABI 45): y[i] = labels[n_id[i]]
- * for i < sizes[0], else `ignore` (written to y[B], as regnn_ns_labels), lse / rowloss as
+ * for i < sizes[0], else `ignore` (written to y[B], as regnn_ns_labels; a label outside [0, C) is
+ * kept in y and its row ignored, here and in regnn_xent_bwd_colsum), lse / rowloss as
  * regnn_softmax_xent_fwd, and out[2] from the last workgroup to finish (ticket: one int32, zero
  * on entry and on return; rows summed in a fixed order). regnn_xent_bwd_colsum: gz as
  * regnn_softmax_xent_bwd, plus gb[c] = sum over rows of gz[r][c] (fixed order) -- out_lin's bias
@@ -640,7 +644,8 @@ int regnn_xent_bwd_colsum(const float* z, const int64_t* y, const float* lse, co
 int regnn_rel_tab(const float* rw, const float* gtab, int32_t n, float alpha, float slope,
                   float* out, hipStream_t stream);
 /* regnn_rel_tab over `count` <= 4 tables (rw[t] of n[t] entries; gtab NULL: forward, else every
- * gtab[t] set: backward) in one launch: every conv layer's relation table at once. */
+ * gtab[t] set: backward) in one launch: every conv layer's relation table at once. A table of
+ * n[t] = 0 entries may pass null pointers. */
 int regnn_rel_tabs(const float* const* rw, const float* const* gtab, float* const* out,
                    const int32_t* n, int32_t count, float alpha, float slope, hipStream_t stream);
 

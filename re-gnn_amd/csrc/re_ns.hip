@@ -1644,7 +1644,12 @@ rel_tab_kernel(const float* __restrict__ rw, const float* __restrict__ gtab, int
 // model's out_lin logits): a wave per row writes lse[r] and the row's loss (0 on an ignored row)
 // and validity; one workgroup then sums them in a fixed order (deterministic) into out = {mean
 // loss, valid count}; backward: gz[r][c] = g / count * (exp(z[r][c] - lse[r]) - [c == y_r]), 0 on
-// ignored rows (a wave per row)
+// ignored rows (a wave per row). A row is ignored when its label is `ignore` or lies outside [0, C)
+// (-1 of an unlabelled ogbn-style node, as the fused step's y >= 0): no kernel indexes z with it.
+__device__ __forceinline__ bool xent_label_on(int64_t yr, int C, int64_t ignore) {
+    return yr != ignore && yr >= 0 && yr < int64_t(C);
+}
+
 __global__ void __launch_bounds__(kBlock)
 xent_rows_kernel(const float* __restrict__ z, const int64_t* __restrict__ y, int B, int C,
                  int64_t ignore, float* __restrict__ lse, float* __restrict__ rowloss) {
@@ -1663,8 +1668,9 @@ xent_rows_kernel(const float* __restrict__ z, const int64_t* __restrict__ y, int
     const float l = m + logf(se);
     if (lane == 0) {
         lse[r] = l;
-        rowloss[r] = yr != ignore ? l - zr[yr] : 0.f;
-        rowloss[B + r] = yr != ignore ? 1.f : 0.f;
+        const bool on = xent_label_on(yr, C, ignore);
+        rowloss[r] = on ? l - zr[yr] : 0.f;
+        rowloss[B + r] = on ? 1.f : 0.f;
     }
 }
 
@@ -1700,7 +1706,7 @@ xent_bwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ y,
     const int r = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= B) return;
     const int64_t yr = y[r];
-    const float scale = yr != ignore ? g[0] / stat[1] : 0.f;
+    const float scale = xent_label_on(yr, C, ignore) ? g[0] / stat[1] : 0.f;
     const float l = lse[r];
     const float* zr = z + int64_t(r) * C;
     float* gr = gz + int64_t(r) * C;
@@ -1735,8 +1741,9 @@ ns_xent_fwd_kernel(const float* __restrict__ z, const int32_t* __restrict__ n_id
         if (lane == 0) {
             y[r] = yr;
             lse[r] = l;
-            rowloss[r] = yr != ignore ? l - zr[yr] : 0.f;
-            rowloss[B + r] = yr != ignore ? 1.f : 0.f;
+            const bool on = xent_label_on(yr, C, ignore);
+            rowloss[r] = on ? l - zr[yr] : 0.f;
+            rowloss[B + r] = on ? 1.f : 0.f;
         }
     }
     // every wave releases its own rows' stores at agent scope (the barrier is workgroup scope),
@@ -1794,7 +1801,7 @@ xent_bwd_colsum_kernel(const float* __restrict__ z, const int64_t* __restrict__ 
 #pragma unroll 4
         for (int r = rl; r < B; r += 16) {
             const int64_t yr = y[r];
-            const float scale = yr != ignore ? gs : 0.f;
+            const float scale = xent_label_on(yr, C, ignore) ? gs : 0.f;
             const float v = scale * (expf(z[int64_t(r) * C + c] - lse[r]) - (int64_t(c) == yr ? 1.f : 0.f));
             gz[int64_t(r) * C + c] = v;
             acc += v;

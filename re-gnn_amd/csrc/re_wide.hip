@@ -261,10 +261,11 @@ int regnn_rel_tabs(const float* const* rw, const float* const* gtab, float* cons
     A.slope = slope;
     A.start[0] = 0;
     for (int t = 0; t < count; ++t) {
-        if (!rw[t] || !out[t] || n[t] < 0) return REGNN_EINVAL;
+        // (an empty table has no storage: its pointers may be null)
+        if (n[t] < 0 || (n[t] > 0 && (!rw[t] || !out[t]))) return REGNN_EINVAL;
         A.rw[t] = rw[t];
         A.g[t] = gtab ? gtab[t] : nullptr;
-        if (gtab && !gtab[t]) return REGNN_EINVAL;
+        if (gtab && !gtab[t] && n[t] > 0) return REGNN_EINVAL;
         A.out[t] = out[t];
         A.start[t + 1] = A.start[t] + n[t];
     }

@@ -1566,9 +1566,17 @@ class NSTrainer:
 
     # -- one step --------------------------------------------------------------------------------
     def _sample(self, slot, before_sums=None):
+        self._deal_targets(slot)
+        self._run_hops(slot, before_sums)
+
+    def _deal_targets(self, slot):
+        """slot's next targets from the epoch permutation (its share of the round robin)."""
         n = len(self.slots)
+        self.slots[slot].batch_from_perm(self.perm, self.rank + slot * self.world, n * self.world)
+
+    def _run_hops(self, slot, before_sums=None):
+        """the hops of slot's current targets, as its engine reads them."""
         s = self.slots[slot]
-        s.batch_from_perm(self.perm, self.rank + slot * self.world, n * self.world)
         if self.fused is not None:
             s.run_hops(before_sums=before_sums)
         else:                                 # the module path reads the CSR blocks

@@ -1314,7 +1314,10 @@ class _SoftmaxXent(torch.autograd.Function):
 
 def softmax_xent(z, y, ignore=-100):
     """nll_loss(log_softmax(z), y, ignore_index) (mean over the non-ignored rows) from fp32 logits
-    in one launch forward and one backward (regnn_softmax_xent_*); y int64."""
+    in one launch forward and one backward (regnn_softmax_xent_*); y int64. A row whose label is
+    `ignore` or lies outside [0, C) (the -1 of an unlabelled node) is ignored: no loss term, a zero
+    gradient row, and z is never indexed with it. With every row ignored the loss is NaN (0 / 0,
+    as nll_loss)."""
     if not (z.is_cuda and z.dim() == 2 and y.dtype == torch.int64):
         raise ValueError("softmax_xent: [B, C] device logits, int64 labels")
     return _SoftmaxXent.apply(z, y, ignore)
@@ -1360,7 +1363,8 @@ def ns_lin_xent(x, w, b, n_id, sizes, labels, ticket, ignore=-100):
     `ignore` past the batch's live targets (mag/regnn_ns.py:346,404-405 over a capacity-sized
     batch): 3 launches forward (GEMM, loss) and 3 backward (loss + bias gradient, two GEMMs).
     x [B, K] fp32, w [C, K], b [C]; n_id / sizes int32, labels int64 device tensors; ticket: one
-    zeroed int32 device word, reused call after call."""
+    zeroed int32 device word, reused call after call. A target whose label lies outside [0, C)
+    (-1 as well as `ignore`) is ignored like the rows past the live count."""
     if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.float32
             and b is not None and n_id.dtype == torch.int32 and labels.dtype == torch.int64 and
             ticket.dtype == torch.int32 and ticket.numel() >= 1):
@@ -2589,15 +2593,29 @@ def copy_many(dst, src):
         L.call("regnn_copy2d_many", ctypes.addressof(arr), len(descs), L.stream())
 
 
+def _zero_past_live(a, live):
+    """a with exact zeros from row `live` on (no host sync): for a product that does not take the
+    live-row bound itself -- torch's, or the x6 GEMM with LIVE_ROWS "off". A capacity-sized
+    operand's rows past the count are unspecified (torch.empty): 0 * NaN in the weight gradient
+    a^T g would be NaN, so they are replaced, not scaled."""
+    if live is None or a.dim() != 2:
+        return a
+    keep = torch.arange(a.shape[0], device=a.device).view(-1, 1) < live.to(a.device).view(1, 1)
+    return torch.where(keep, a, a.new_zeros(()))
+
+
 def linear(x, w, bias=None, live=None):
     """nn.functional.linear on regnn_gemm_x6 when the operands allow it (else torch). live: a
-    one-element int32 device tensor with x's live rows (_LinearX6; torch's product ignores it)."""
+    one-element int32 device tensor with x's live rows (_LinearX6; any other product gets x with
+    its rows past the count zeroed)."""
     if (GEMM_X6["mode"] != "off" and x.dim() == 2 and gemm_x6_ok(x, w) and
             (bias is None or (bias.is_cuda and bias.dtype == torch.float32 and bias.dim() == 1))):
         live_ok = (live is not None and live.is_cuda and live.dtype == torch.int32 and
                    live.numel() == 1 and LIVE_ROWS["mode"] != "off")
-        return _LinearX6.apply(x, w, bias, live if live_ok else None)
-    return torch.nn.functional.linear(x, w, bias)
+        if live_ok:
+            return _LinearX6.apply(x, w, bias, live)
+        return _LinearX6.apply(_zero_past_live(x, live).contiguous(), w, bias, None)
+    return torch.nn.functional.linear(_zero_past_live(x, live), w, bias)
 
 
 # products of at most SMALL_BLAS["macs"] multiply-adds without a live-row bound (the wide NS
@@ -2610,7 +2628,9 @@ SMALL_BLAS = {"mode": os.environ.get("REGNN_GEMM_SMALL_BLAS", "on"),
 
 def mm(a, b, c=None, live=None):
     """c + a @ b on regnn_gemm_x6 when the operands allow it (else torch). live: a one-element
-    int32 device tensor with a's live rows (a's rows past it are zero: the GEMMs skip them)."""
+    int32 device tensor with a's live rows (a's rows up to the next multiple of 128 past it are
+    zero, the rest unspecified: the x6 GEMM skips them, any other product gets a with every row
+    past the count zeroed)."""
     # c: None, a length-N row vector or exactly [M, N] (the x6 epilogue writes M rows with c's
     # row stride; any other broadcastable shape goes to torch)
     M, N = (a.shape[0], b.shape[1]) if a.dim() == 2 and b.dim() == 2 else (-1, -1)
@@ -2623,7 +2643,11 @@ def mm(a, b, c=None, live=None):
     if GEMM_X6["mode"] != "off" and gemm_x6_ok(a, b) and c_ok and not small:
         live_ok = (live is not None and live.is_cuda and live.dtype == torch.int32 and
                    live.numel() == 1 and LIVE_ROWS["mode"] != "off")
-        return _MMx6.apply(a, b, c, live if live_ok else None)
+        if live_ok:
+            return _MMx6.apply(a, b, c, live)
+        return _MMx6.apply(_zero_past_live(a, live).contiguous(), b, c, None)
+    # (torch's product reads every row of a: the unspecified ones are zeroed first)
+    a = _zero_past_live(a, live)
     return a @ b if c is None else (torch.addmm(c, a, b) if c.dim() <= 2 else c + a @ b)
 
 
@@ -2650,6 +2674,7 @@ class _WideLn(torch.autograd.Function):
                L.ptr(stats), L.ptr(y), L.ptr(live), L.stream())
         ctx.save_for_backward(a, stats, rs, gamma, beta, state, live)
         ctx.layer, ctx.p, ctx.has_res = int(layer), float(p), res is not None
+        ctx.has_bias = bias is not None
         return y
 
     @staticmethod
@@ -2668,7 +2693,9 @@ class _WideLn(torch.autograd.Function):
                L.ptr(slab), L.ptr(live), L.stream())
         sums = _reduce(slab, 3 * H)
         g_bias, g_gamma, g_beta = sums[:H], sums[H:2 * H], sums[2 * H:]
-        return (gx, g_bias, gres, g_gamma, g_beta, None, None, None, None, None)
+        # (bias None: no gradient for it -- autograd refuses one for an input that is no tensor)
+        return (gx, g_bias if ctx.has_bias else None, gres, g_gamma, g_beta, None, None, None,
+                None, None)
 
 
 def wide_ln_ok(x, ln, bias=None):

@@ -130,8 +130,8 @@ def sample(case):
 
 
 def build_model(case, dtype):
-    m = RefModel(case["k_in"], HIDDEN, case["C"], case["L"], ALPHA, case["dropout"], case["T"],
-                 case["n_et"], residual=case["residual"]).to(dtype)
+    m = RefModel(case["k_in"], case.get("hidden", HIDDEN), case["C"], case["L"], ALPHA,
+                 case["dropout"], case["T"], case["n_et"], residual=case["residual"]).to(dtype)
     assert {n for n, _ in m.named_parameters()} == set(case["params"])
     with torch.no_grad():
         for n, p in m.named_parameters():
@@ -248,7 +248,7 @@ def _pair_table(rng, T, n_et, src_ok, dst_ok):
 
 def make_case(T, k_in, L, C, n_edge_types, B, sizes, schema, *, residual=False, dropout=0.0,
               unlabelled=None, absent_type=None, empty_type=None, n_nodes=3000, deg=12,
-              min_deg=0, seed=0, name=""):
+              min_deg=0, seed=0, name="", hidden=HIDDEN, hub_fanin=18):
     """A small typed graph (numpy only), one batch and a model's parameters.
 
     Node ids grouped by type, local = id - type offset, labels -1 outside type 0; relations per
@@ -260,9 +260,11 @@ def make_case(T, k_in, L, C, n_edge_types, B, sizes, schema, *, residual=False, 
     The batch opens with a target without in-edges, a hub (an in-neighbour of itself twice and of
     the low-degree targets below: with its self loop, its row of hop 0's transposed index holds
     17+ entries from B = 17 on, where 14 of them are other targets), a target with more in-edges
-    than any fan-out, then up to 18 low-degree targets (<= 3 in-edges + the hub); the rest is
-    drawn at random from type 0. min_deg: a floor under every other node's in-degree. What B
-    allows of this is asserted below and recorded in case["edges"]."""
+    than any fan-out, then up to hub_fanin (18) low-degree targets (<= 3 in-edges + the hub); the
+    rest is drawn at random from type 0. min_deg: a floor under every other node's in-degree. What
+    B allows of this is asserted below and recorded in case["edges"]. hidden: the model's width
+    (64: the fused step's); it shapes the parameters only, so at 64 and hub_fanin 18 every array
+    is the one the builder always drew (tests/test_cpu_nsmod_ref.py pins their hashes)."""
     assert schema in ("slots", "random") and len(sizes) == L
     rng = np.random.default_rng(1000 + seed)
     n_et = int(n_edge_types)
@@ -281,7 +283,7 @@ def make_case(T, k_in, L, C, n_edge_types, B, sizes, schema, *, residual=False, 
     heavy = rng.random(N) < 0.05
     d[heavy] = rng.integers(3 * deg, 4 * deg + 1, int(heavy.sum()))
     d = np.maximum(d, min_deg)                         # (the special targets below keep theirs)
-    n_low = max(0, min(18, B - 3))
+    n_low = max(0, min(int(hub_fanin), B - 3))
     z, hub, hi = 0, 1, 2
     low = np.arange(3, 3 + n_low)
     # (the hub's and the low targets' rows stay below the first fan-out: every edge is sampled)
@@ -335,7 +337,7 @@ def make_case(T, k_in, L, C, n_edge_types, B, sizes, schema, *, residual=False, 
     x = [rng.standard_normal((max(int(c), 1), k_in)).astype(np.float32) for c in counts]
     with torch.random.fork_rng():                      # (the caller's torch RNG stays as it was)
         torch.manual_seed(seed)
-        m = RefModel(k_in, HIDDEN, C, L, ALPHA, dropout, T, n_et, residual=residual)
+        m = RefModel(k_in, hidden, C, L, ALPHA, dropout, T, n_et, residual=residual)
     n_rel = n_et + T
     with torch.no_grad():
         for c in m.convs:
@@ -343,16 +345,17 @@ def make_case(T, k_in, L, C, n_edge_types, B, sizes, schema, *, residual=False, 
             sign = np.where(rng.random(n_rel) < 0.3, -1.0, 1.0)
             sign[0], sign[-1] = 1.0, -1.0              # both LeakyReLU slopes, whatever the draw
             c.relation_weight.copy_(torch.from_numpy(mag * sign))
-            c.bias.copy_(torch.from_numpy(rng.normal(0, 0.1, HIDDEN)))
-            c.norm.weight.copy_(torch.from_numpy(1 + rng.normal(0, 0.2, HIDDEN)))
-            c.norm.bias.copy_(torch.from_numpy(rng.normal(0, 0.1, HIDDEN)))
+            c.bias.copy_(torch.from_numpy(rng.normal(0, 0.1, hidden)))
+            c.norm.weight.copy_(torch.from_numpy(1 + rng.normal(0, 0.2, hidden)))
+            c.norm.bias.copy_(torch.from_numpy(rng.normal(0, 0.1, hidden)))
     params = {n: p.detach().numpy().copy() for n, p in m.named_parameters()}
     case = dict(name=name, T=T, k_in=k_in, L=L, C=C, n_et=n_et, B=B, sizes=list(sizes),
                 schema=schema, residual=residual, dropout=dropout, unlabelled=unlabelled,
                 absent_type=absent_type, empty_type=empty_type, N=N, counts=counts, off=off,
                 ntype=ntype, local=local, src=src, dst=dst, etype=rel, ptr=ptr, idx=src,
                 labels=labels, batch=batch.astype(np.int64), x=x, params=params,
-                seed=4242 + seed, epoch=1, batch_idx=3, pairs=pairs)
+                seed=4242 + seed, epoch=1, batch_idx=3, pairs=pairs, hidden=int(hidden),
+                hub_fanin=int(hub_fanin))
     case["edges"] = _check_edges(case)
     return case
 

@@ -31,7 +31,7 @@ def _setup(case):
     assert torch.equal(rg.csr_ptr.cpu().long(), torch.from_numpy(case["ptr"]))
     ds = DeviceSampler(rg, case["sizes"], case["B"], etype=torch.from_numpy(case["etype"]),
                        ntype=torch.from_numpy(case["ntype"]), num_edge_types=case["n_et"])
-    model = mag.REGNN(K, R.HIDDEN, case["C"], L, R.ALPHA, case["dropout"],
+    model = mag.REGNN(K, case.get("hidden", R.HIDDEN), case["C"], L, R.ALPHA, case["dropout"],
                       {t: K for t in range(T)}, case["n_et"], residual=case["residual"],
                       use_norm="ln", self_loop_type=2)
     assert {n for n, _ in model.named_parameters()} == set(case["params"])
