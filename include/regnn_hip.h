@@ -712,6 +712,33 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                  int32_t* csc_ent, int32_t* csc_long, int32_t* csc_rank, int32_t strided,
                  hipStream_t stream);
 
+/* The CSR hop that appends no self loop (mag self_loop_type 1 and 3, mag/regnn_layers.py:86-99:
+ * type 1's loops are edges of the graph under relations of their own and are sampled like any
+ * other edge; type 3 has none). regnn_ns_hop's arguments without local / edge_type / edge_off /
+ * meta_only / csc_* / strided, the same buffer sizes (cap_e = cap_dst (k + 1), an upper bound
+ * here), the same six launches (sample, row offsets, place, flags, scan / append, resolve) and
+ * the same sampler spec, bit-identical to oracle/sampler_oracle.py. ntype is not read and may be
+ * NULL. The block:
+ *   row i < sizes[hop] holds exactly its scnt[i] sampled entries, ascending CSR position;
+ *   blk_rel = the edge type, blk_pos >= 0 and gsrc >= 0 for every entry (none is a loop);
+ *   inv[i] = 1 / max(scnt[i], 1) (torch_scatter mean's divisor: an empty row aggregates to 0),
+ *   inv[i] = 1 for sizes[hop] <= i < cap_dst;
+ *   blk_ptr[i] == blk_ptr[i + 1] for a row without sampled entries, blk_ptr [cap_dst + 1] as in
+ *   regnn_ns_hop (rows past sizes[hop] are empty);
+ *   sizes[8 + hop] = the sampled entries, also added to state[5]; sizes[hop + 1] = sizes[hop] +
+ *   the new sources (a block without any entry is valid: E = 0, sizes[hop + 1] = sizes[hop]).
+ * Every consumer of a CSR block (regnn_ns_gat_*, regnn_ns_gatv2_*, regnn_ns_block_tidx,
+ * regnn_ns_typed_agg*, regnn_spmm_fwd / regnn_ns_spmm_bwd) writes exact zeros for an empty row.
+ * REGNN_EINVAL for a NULL pointer (ntype aside), cap_dst <= 0, hop outside [0, 6];
+ * REGNN_EUNSUPPORTED for k outside [1, 64] or cap_e >= 2^31; both before any launch. */
+int regnn_ns_hop_noloop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                        const int32_t* ntype, int32_t num_edge_types, int32_t k, int32_t hop,
+                        int64_t* state, int32_t* sizes, int32_t* n_id, int32_t cap_dst,
+                        uint64_t* g2l, uint64_t* first, int32_t* samp, int32_t* spos,
+                        int32_t* scnt, int32_t* gsrc, uint8_t* flag, int32_t* tiles,
+                        uint64_t* status, int32_t* blk_ptr, int32_t* blk_idx, uint8_t* blk_rel,
+                        int32_t* blk_pos, int32_t* blk_row, float* inv, hipStream_t stream);
+
 /* The fused step's outer (meta-only, strided) hop with layer 0's parameter-free input sums
  * (relation slots: each (target type, source type) pair has one relation). Samples hop `hop` as
  * regnn_ns_hop(meta_only = 1, strided = 1) does -- the same slots, scnt, inv, blk_rel, edge_type /

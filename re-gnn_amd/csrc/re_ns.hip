@@ -294,6 +294,9 @@ ns_sample_strided_kernel(const int32_t* __restrict__ ptr, const int32_t* __restr
 // exact in any order). status[tile] = stamp << 32 | kind << 30 | value, kind 1 = the tile's own
 // count, 2 = inclusive prefix; entries of another stamp are stale (nothing is reset between
 // steps). A block only waits on lower tiles, which were dispatched before it.
+// LOOP = false (regnn_ns_hop_noloop, self_loop_type 1 / 3): a row holds its sampled entries only --
+// the row's count is scnt, no loop entry is written (ntype / local / e_type unread), and inv =
+// 1 / max(cnt, 1) (torch_scatter mean's divisor: an empty row aggregates to 0).
 constexpr int kNsRowsIT = 4;
 constexpr int kNsRowsTile = kBlock * kNsRowsIT;
 
@@ -301,6 +304,7 @@ __device__ __forceinline__ uint64_t lb_pack(uint32_t stamp, uint32_t kind, uint3
     return (uint64_t(stamp) << 32) | (uint64_t(kind) << 30) | uint64_t(v);
 }
 
+template <bool LOOP>
 __global__ void __launch_bounds__(kBlock)
 ns_rows_kernel(const int32_t* __restrict__ scnt, const int32_t* __restrict__ n_id,
                const int32_t* __restrict__ ntype, int num_edge_types, int32_t* __restrict__ sizes,
@@ -327,14 +331,14 @@ ns_rows_kernel(const int32_t* __restrict__ scnt, const int32_t* __restrict__ n_i
     for (int j = 0; j < kNsRowsIT; ++j) {
         const int i = i0 + j;
         const bool live = i < cap && i < n;
-        vals[j] = live ? scnt[i] + 1 : 0;
+        vals[j] = live ? scnt[i] + (LOOP ? 1 : 0) : 0;
         gids[j] = live ? n_id[i] : 0;
         s += vals[j];
     }
 #pragma unroll
     for (int j = 0; j < kNsRowsIT; ++j) {
-        rels[j] = vals[j] ? ntype[gids[j]] : 0;
-        offs[j] = vals[j] && local ? local[gids[j]] : 0;
+        rels[j] = LOOP && vals[j] ? ntype[gids[j]] : 0;
+        offs[j] = LOOP && vals[j] && local ? local[gids[j]] : 0;
     }
     int total;
     const int ex = block_exscan<kBlock>(s, lds, &total);
@@ -366,7 +370,9 @@ ns_rows_kernel(const int32_t* __restrict__ scnt, const int32_t* __restrict__ n_i
         const int i = i0 + j;
         if (i < cap) {
             blk_ptr[i] = off;
-            if (i < n) {
+            if (!LOOP) {
+                inv[i] = i < n && vals[j] > 1 ? 1.f / float(vals[j]) : 1.f;
+            } else if (i < n) {
                 const int lp = off + vals[j] - 1;      // the self loop closes the row
                 blk_idx[lp] = i;
                 blk_rel[lp] = uint8_t(rels[j] + num_edge_types);
@@ -2034,7 +2040,7 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
     hipLaunchKernelGGL(ns_sample_kernel, dim3((cap_dst + 3) / 4), dim3(kBlock), 0, stream, ptr,
                        idx, n_id, sizes, hop, cap_dst, k, state, g2l, samp, spos, scnt);
     REGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ns_rows_kernel, dim3((cap_dst + kNsRowsTile - 1) / kNsRowsTile),
+    hipLaunchKernelGGL(ns_rows_kernel<true>, dim3((cap_dst + kNsRowsTile - 1) / kNsRowsTile),
                        dim3(kBlock), 0, stream, scnt, n_id, ntype, num_edge_types, sizes, hop,
                        cap_dst, state, blk_ptr, blk_idx, blk_rel, blk_pos, blk_row, gsrc, inv, status, local,
                        edge_type, edge_off, lean, csc_cnt, int(cap_e));
@@ -2061,6 +2067,52 @@ int regnn_ns_hop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
                            blk_row, blk_rel, csc_cnt, csc_ptr, csc_ent, csc_long, 0);
         REGNN_LAUNCH_CHECK();
     }
+    return REGNN_OK;
+}
+
+// the CSR hop without the appended self loop (self_loop_type 1 / 3): regnn_ns_hop's CSR chain with
+// ns_rows_kernel<false>; the other five kernels as they are (no entry has gsrc < 0, so
+// ns_resolve_kernel's loop branch is never taken)
+int regnn_ns_hop_noloop(const int32_t* ptr, const int32_t* idx, const uint8_t* etype,
+                        const int32_t* ntype, int32_t num_edge_types, int32_t k, int32_t hop,
+                        int64_t* state, int32_t* sizes, int32_t* n_id, int32_t cap_dst,
+                        uint64_t* g2l, uint64_t* first, int32_t* samp, int32_t* spos,
+                        int32_t* scnt, int32_t* gsrc, uint8_t* flag, int32_t* tiles,
+                        uint64_t* status, int32_t* blk_ptr, int32_t* blk_idx, uint8_t* blk_rel,
+                        int32_t* blk_pos, int32_t* blk_row, float* inv, hipStream_t stream) {
+    if (!ptr || !idx || !etype || !state || !sizes || !n_id || !g2l || !first || !samp || !spos ||
+        !scnt || !gsrc || !flag || !tiles || !status || !blk_ptr || !blk_idx || !blk_rel ||
+        !blk_pos || !blk_row || !inv || cap_dst <= 0 || hop < 0 || hop > 6 || num_edge_types < 0)
+        return REGNN_EINVAL;
+    if (k < 1 || k > 64) return REGNN_EUNSUPPORTED;
+    // the buffers are sized as regnn_ns_hop's (an upper bound here: a row holds <= k entries)
+    const int64_t cap_e = int64_t(cap_dst) * (k + 1);
+    if (cap_e >= (int64_t(1) << 31)) return REGNN_EUNSUPPORTED;
+    const int n_tiles = int((cap_e + kNsTile - 1) / kNsTile);
+    hipLaunchKernelGGL(ns_sample_kernel, dim3((cap_dst + 3) / 4), dim3(kBlock), 0, stream, ptr,
+                       idx, n_id, sizes, hop, cap_dst, k, state, g2l, samp, spos, scnt);
+    REGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ns_rows_kernel<false>, dim3((cap_dst + kNsRowsTile - 1) / kNsRowsTile),
+                       dim3(kBlock), 0, stream, scnt, n_id, ntype, num_edge_types, sizes, hop,
+                       cap_dst, state, blk_ptr, blk_idx, blk_rel, blk_pos, blk_row, gsrc, inv,
+                       status, nullptr, nullptr, nullptr, 0, nullptr, int(cap_e));
+    REGNN_LAUNCH_CHECK();
+    const int64_t slots = int64_t(cap_dst) * k;
+    hipLaunchKernelGGL(ns_place_kernel, dim3(unsigned((slots + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, stream, samp, spos, scnt, sizes, hop, cap_dst, k, state,
+                       etype, g2l, first, blk_ptr, blk_rel, blk_pos, blk_row, gsrc, ntype, nullptr,
+                       nullptr, nullptr, 0);
+    REGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ns_flags_kernel, dim3(n_tiles), dim3(kBlock), 0, stream, gsrc, sizes, hop,
+                       state, g2l, first, flag, tiles, n_tiles, 0);
+    REGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ns_finish_kernel, dim3(n_tiles), dim3(kBlock), 0, stream, gsrc, sizes, hop,
+                       state, flag, tiles, g2l, n_id, 0);
+    REGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ns_resolve_kernel, dim3(unsigned((cap_e + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, stream, gsrc, sizes, hop, g2l, blk_idx, int(cap_e), ntype,
+                       nullptr, nullptr, nullptr, nullptr, 0);
+    REGNN_LAUNCH_CHECK();
     return REGNN_OK;
 }
 

@@ -116,6 +116,8 @@ _SIG = {
     "regnn_xent_bwd_colsum": ([P, P, P, P, P, I32, I32, I64, P, P, P], ctypes.c_int),
     "regnn_ns_hop": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P,
                       P, P, P, P, P, P, I32, P, P, P, P, P, I32, P], ctypes.c_int),
+    "regnn_ns_hop_noloop": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P,
+                             P, P, P, P, P, P, P], ctypes.c_int),
     "regnn_ns_hop_typed_sums": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P,
                                  I32, I32, P, P, P, P, P, P, P], ctypes.c_int),
     "regnn_ns_hop_typed_sums_dt": ([P, P, P, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P,

@@ -17,6 +17,8 @@ the rows it owns. The aggregation is the same HIP SpMM as training (relation tab
 and bias fused; hub rows through the chunk + tree path). Each block holds the rank's CSR row
 range with the target self loops appended last in every row, as the sampled blocks do
 (mag/regnn_layers.py:90-96), so a rank's output rows equal the reference's batch outputs.
+A model of self_loop_type 1 / 3 (accepted with mag.NOLOOP_BLOCKS on) appends nothing (mag/regnn_layers.py:86-99): its blocks are the
+rank's CSR rows as they are, the mean's divisor max(in-count, 1).
 
 The attention models ('regat', 'regatv2'; mag/regnn_layers.py:253-325, 394-436) exchange the
 projected rows xs = x @ lin_src.weight^T the same way; a layer is then
@@ -57,17 +59,30 @@ def shard_bounds(csr_ptr, world):
 class RowBlock:
     """Forward-only CSR of destination rows [r0, r1) of a global graph (all N nodes as sources),
     a self loop appended last in every row with relation type ntype + num_edge_types.
+    self_loops=False (mag self_loop_type 1 / 3): the rows as they are, nothing appended, and
+    inv = 1 / max(in-count, 1) (torch_scatter mean: a row without in-edges aggregates to 0).
 
     Exposes what ops.re_spmm's forward reads (RelGraph-compatible: csr_ptr / csr_idx / csr_plan /
     n_src / n_dst / E, and pack.rel_csr with 0-based relation ids)."""
 
-    def __init__(self, rg, r0, r1, edge_type_csr, node_type, num_edge_types):
+    def __init__(self, rg, r0, r1, edge_type_csr, node_type, num_edge_types, self_loops=True):
         dev = rg.device
+        self.self_loops = bool(self_loops)
         ptr = rg.csr_ptr.to(torch.int64)
         e0, e1 = int(ptr[r0].item()), int(ptr[r1].item())
         n = r1 - r0
         M = e1 - e0
         cnt = ptr[r0 + 1:r1 + 1] - ptr[r0:r1]
+        if not self.self_loops:
+            self.device, self.r0, self.r1 = dev, r0, r1
+            self.n_src, self.n_dst, self.E = rg.n_src, n, M
+            self.csr_ptr = (ptr[r0:r1 + 1] - e0).to(torch.int32).contiguous()
+            self.csr_idx = rg.csr_idx[e0:e1].to(torch.int32).contiguous()
+            self.csr_plan = SegPlan(self.csr_ptr)
+            self.pack = type("RowPack", (), {})()
+            self.pack.rel_csr = _word_padded(edge_type_csr[e0:e1].to(torch.uint8).contiguous())
+            self._inv = (1.0 / cnt.clamp(min=1).to(torch.float32)).contiguous()
+            return
         newptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         torch.cumsum(cnt + 1, 0, out=newptr[1:])
         row_of = torch.repeat_interleave(torch.arange(n, device=dev), cnt, output_size=M)
@@ -129,15 +144,23 @@ class ShardedInference:
         if self.kind not in ("regcn", "regat", "regatv2"):
             raise NotImplementedError(f"sharded full-neighbour inference: model {self.kind!r}")
         if model.self_loop_type != 2:
-            raise NotImplementedError("full-neighbour inference is built for self_loop_type=2 "
-                                      "(the mag/regnn_ns.py default)")
+            from . import mag
+            if model.self_loop_type not in (1, 3) or not mag.noloop_blocks_on():
+                raise NotImplementedError(
+                    "full-neighbour inference is built for self_loop_type=2 (the "
+                    "mag/regnn_ns.py default); REGNN_NOLOOP_BLOCKS=on (mag.NOLOOP_BLOCKS) "
+                    "evaluates types 1 / 3 over loop-less row blocks")
         self.model, self.rank, self.world = model, rank, world
         self.node_type, self.local_node_idx = node_type, local_node_idx
         self.bounds = bounds if bounds is not None else shard_bounds(rg.csr_ptr, world)
         r0, r1 = self.bounds[rank], self.bounds[rank + 1]
         self.r0, self.r1 = r0, r1
         et_csr = edge_type.to(rg.device)[rg.csr_eid].to(torch.uint8)
-        self.block = RowBlock(rg, r0, r1, et_csr, node_type, model.num_edge_types)
+        # self_loop_type 2: the target's self loop closes every row; 1 / 3: the graph's own
+        # in-edges only (type 1's loops are edges of the graph under relations of their own), a
+        # node without in-edges gets bias (+ residual) / the zero attention term
+        self.block = RowBlock(rg, r0, r1, et_csr, node_type, model.num_edge_types,
+                              self_loops=model.self_loop_type == 2)
         self.own = torch.arange(r0, r1, device=rg.device)
 
     @torch.no_grad()

@@ -33,6 +33,48 @@ def make_block(edge_index, edge_type, target_node_type, n_src, n_dst, num_edge_t
     return rg, pack
 
 
+def block_matches(blk, self_loop_type):
+    """True where a device-sampled NSBlock carries what a conv of this self_loop_type aggregates:
+    type 2 reads blocks whose rows end with their self loop (DeviceSampler()), types 1 / 3 blocks
+    of sampled entries only (DeviceSampler(self_loops=False); mag/regnn_layers.py:86-99)."""
+    return bool(getattr(blk, "self_loops", True)) == (self_loop_type == 2)
+
+
+def _check_block(blk, self_loop_type):
+    """a conv never aggregates a block of the other form (either direction)"""
+    if not block_matches(blk, self_loop_type):
+        have = bool(getattr(blk, "self_loops", True))
+        raise ValueError(
+            f"this conv has self_loop_type {self_loop_type}, which reads blocks "
+            f"{'with' if self_loop_type == 2 else 'without'} appended self loops, but the "
+            f"device-sampled block has self_loops={have} (DeviceSampler(self_loops="
+            f"{self_loop_type == 2}) writes the matching ones)")
+
+
+def add_self_loop_relations(edge_index, edge_type, node_type, num_edge_types, rel_of_type=None):
+    """self_loop_type 1's graph (mag/regnn_ns.py:107-119, before group_hetero_graph): one (v, v)
+    edge per node appended after the caller's edges, with relation num_edge_types +
+    rel_of_type[node type]. rel_of_type (default: the identity) maps a node type to the position
+    of its self-loop relation among the appended ones -- the reference numbers relations in
+    edge_index_dict order, so ogbn-mag's loops come out as author, field_of_study, institution,
+    paper. Returns (edge_index', edge_type', num_edge_types'), num_edge_types' = num_edge_types +
+    the number of self-loop relations."""
+    node_type = torch.as_tensor(node_type).to(edge_index.device, torch.int64).reshape(-1)
+    n_types = int(node_type.max().item()) + 1 if node_type.numel() else 0
+    if rel_of_type is None:
+        rot = torch.arange(n_types, device=edge_index.device)
+    else:
+        rot = torch.as_tensor(rel_of_type).to(edge_index.device, torch.int64).reshape(-1)
+        if rot.numel() < n_types:
+            raise ValueError(f"rel_of_type has {rot.numel()} entries for {n_types} node types")
+    loop = torch.arange(node_type.numel(), device=edge_index.device, dtype=edge_index.dtype)
+    ei = torch.cat([edge_index, torch.stack([loop, loop])], 1)
+    et = torch.cat([edge_type.reshape(-1),
+                    (rot[node_type] + int(num_edge_types)).to(edge_type.dtype)])
+    n_loop_rel = int(rot[:n_types].max().item()) + 1 if n_types else 0
+    return ei, et, int(num_edge_types) + n_loop_rel
+
+
 class REGCNConv(torch.nn.Module):
     """mag/regnn_layers.py:24-150 (same constructor, parameters and forward signature)."""
 
@@ -81,6 +123,9 @@ class REGCNConv(torch.nn.Module):
             # reference projects every source row first, :101-107), so the GEMM and its two
             # backward GEMMs run over the block's targets, not its sources (~11x fewer rows at
             # fan-out [25, 20]); the residual x_target W folds into the same product (:104,131)
+            # (self_loop_type 1 / 3 on a loop-less block: a row without entries aggregates to 0,
+            # torch_scatter mean's result, and comes out bias (+ residual))
+            _check_block(edge_index, self.self_loop_type)
             agg = ops.ns_spmm(edge_index, x_src, tab)
             if self.residual:
                 agg = agg + x_target
@@ -121,6 +166,7 @@ class REGCNConv(torch.nn.Module):
         table when the caller formed it (ops.rel_tabs)."""
         if tab is None:
             tab = ops.rel_tab(self.relation_weight, self.scaling_factor)        # :110-111
+        _check_block(blk, self.self_loop_type)
         agg = ops.ns_spmm(blk, x_src, tab)
         if self.residual:
             agg = agg + x_target
@@ -250,13 +296,12 @@ class REGATConv(torch.nn.Module):
 
     def _block_attention(self, blk, x_src, x_dst, tab, n_dst, return_weights):
         """out [n_dst, H, C] over a device-sampled NSBlock (self_loop_type 2: the sampler's
-        blocks carry the targets' self loops with relation num_edge_types + node type)."""
+        blocks carry the targets' self loops with relation num_edge_types + node type; 1 / 3: a
+        loop-less block, where a row without entries gets the zero attention term)."""
         if return_weights:
             raise ValueError("return_weights needs the edge_index / edge_type tensors, not a "
                              "device-sampled block")
-        if self.self_loop_type != 2:
-            raise ValueError("a device-sampled block holds self_loop_type 2's self loops; this "
-                             f"conv has self_loop_type {self.self_loop_type}")
+        _check_block(blk, self.self_loop_type)
         if blk.n_dst != n_dst:
             raise ValueError(f"the block has {blk.n_dst} target rows, x_target {n_dst}")
         # a_s over the capacity-sized source rows in one pass each way (regnn_attn_dots_fwd /
@@ -269,6 +314,8 @@ class REGATConv(torch.nn.Module):
                 return_weights=False):
         H, C = self.heads, self.out_channels
         ns_block = getattr(edge_index, "is_ns_block", False)
+        if ns_block and (not self.v2 or GATV2_BLOCKS["mode"] == "on"):
+            _check_block(edge_index, self.self_loop_type)       # before any launch
         if isinstance(x, torch.Tensor):
             x_src = x_dst = self.lin_src(x).view(-1, H, C)
             n_dst = x.shape[0]
@@ -338,9 +385,7 @@ class REGATv2Conv(REGATConv):
         if return_weights:
             raise ValueError("return_weights needs the edge_index / edge_type tensors, not a "
                              "device-sampled block")
-        if self.self_loop_type != 2:
-            raise ValueError("a device-sampled block holds self_loop_type 2's self loops; this "
-                             f"conv has self_loop_type {self.self_loop_type}")
+        _check_block(blk, self.self_loop_type)
         if blk.n_dst != n_dst:
             raise ValueError(f"the block has {blk.n_dst} target rows, x_target {n_dst}")
         return ops.ns_gatv2(blk, x_src, x_dst, self.att, tab, self.negative_slope)   # :399-417
@@ -354,6 +399,20 @@ class REGATv2Conv(REGATConv):
 # _bwd), and NSTrainer(device_blocks=True) takes 'regatv2' models; "off" (the default): the conv
 # refuses a block and 'regatv2' trains on the exact-size path, as before the operator existed
 GATV2_BLOCKS = {"mode": os.environ.get("REGNN_GATV2_BLOCKS", "off")}
+# "on": models of self_loop_type 1 / 3 get their device path -- NSTrainer(device_blocks=True) trains
+# them on loop-less blocks (DeviceSampler(self_loops=False), regnn_ns_hop_noloop) and
+# ShardedInference (REGNN.inference / inference_sharded) evaluates them; "off" (the default):
+# both refuse such a model with the reason, as before the loop-less hop existed
+NOLOOP_BLOCKS = {"mode": os.environ.get("REGNN_NOLOOP_BLOCKS", "off")}
+
+
+def noloop_blocks_on():
+    """NOLOOP_BLOCKS as a bool; any value but "on" / "off" is an error at first use"""
+    mode = NOLOOP_BLOCKS["mode"]
+    if mode not in ("on", "off"):
+        raise ValueError(f"REGNN_NOLOOP_BLOCKS / mag.NOLOOP_BLOCKS must be 'on' or 'off', "
+                         f"got {mode!r}")
+    return mode == "on"
 # "auto": layer 0 of a device-block REGNN (regcn, self-loop type 2, feats_type 3) aggregates the
 # raw input rows per node type and projects after (REGNN._typed_first_layer); "off": group_input
 # over every sampled node first, as the reference orders it (tests compare the two)
@@ -579,12 +638,20 @@ class REGNN(torch.nn.Module):
         sampled raw row, no per-node projection) and the composed W_t^T W_0 runs over the
         block's target rows only (~13 k of ~280 k sampled rows at fan-out [25, 20])."""
         if (TYPED_AGG["mode"] == "off" or self.model != 'regcn' or self.feats_type == 2 or
-                self.self_loop_type != 2 or not adjs):
+                not adjs):
             return None
         edge_index, _e_id, _size = adjs[0]
         blk = edge_index if getattr(edge_index, "is_ns_block", False) else \
             getattr(adjs[0], "block", None)
         if blk is None or getattr(blk, "inv", None) is None:
+            return None
+        if not block_matches(blk, self.self_loop_type):
+            return None
+        if self.self_loop_type != 2 and (
+                getattr(blk, "pre_sums", None) is not None or
+                getattr(blk, "edge_meta", None) is not None or
+                self.convs[0].relation_weight.numel() != self.num_edge_types):
+            # a loop-less block in the plain form only: ops.ns_typed_agg by n_id
             return None
         tabs = self._type_tables(x_dict)
         # (with blk.pre_sums the tables are never read here: they may be bf16; without, bf16
@@ -690,7 +757,7 @@ class REGNN(torch.nn.Module):
             blk = edge_index if getattr(edge_index, "is_ns_block", False) else \
                 getattr(adj, "block", None)
             if (blk is not None and getattr(blk, "is_ns_block", False) and epi is not None and
-                    self.self_loop_type == 2 and
+                    block_matches(blk, self.self_loop_type) and
                     (self.convs[i]._bn_live(blk) or
                      ops.wide_ln_ok(x, self.convs[i].norm, self.convs[i].bias))):
                 ep = self._wide_epi(blk) or epi
@@ -701,7 +768,10 @@ class REGNN(torch.nn.Module):
             # on: ops.ns_gatv2 -- only where the adj IS the block,
             # NSTrainer(device_blocks=True); a PyG-style Adj carrying one keeps the exact-size
             # path)
-            if (blk is not None and self.self_loop_type == 2 and
+            if blk is not None and blk is edge_index:
+                # the adj IS a device block: one of the other form is refused, never aggregated
+                _check_block(blk, self.self_loop_type)
+            if (blk is not None and block_matches(blk, self.self_loop_type) and
                     (self.model == 'regcn' or
                      (self.model == 'regat' and blk is edge_index) or
                      (self.model == 'regatv2' and blk is edge_index and
@@ -734,7 +804,9 @@ class REGNN(torch.nn.Module):
         sizes=[-1] over all nodes) or the global RelGraph itself. Its batches are row ranges of
         the full graph, so each layer runs as one full-graph aggregation with the layer input
         resident in HBM (regnn_hip/inference.py); ``inference_sharded`` splits the rows over
-        data-parallel ranks. All three models (self_loop_type 2): 'regcn' runs the fused mean
+        data-parallel ranks. All three models; self_loop_type 2: each row closed by the target's
+        self loop; 1 / 3, with NOLOOP_BLOCKS on: the rows as they are, a node without in-edges
+        aggregating to zero (refused with the knob off). 'regcn' runs the fused mean
         SpMM, 'regat' / 'regatv2' the forward-only fused attention (ops.mag_attn_scores +
         the epilogue). The attention softmax subtracts ONE maximum over every entry and head
         (mag/utils.py:45-57); here it is the maximum over the whole graph, i.e. the reference

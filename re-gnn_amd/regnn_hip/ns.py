@@ -45,6 +45,11 @@ class NSBlock:
 
     is_ns_block = True
 
+    # True: every row ends with its self loop (self_loop_type 2, what DeviceSampler() writes);
+    # False: sampled entries only, inv = 1 / max(sampled, 1) (DeviceSampler(self_loops=False):
+    # self_loop_type 1 / 3)
+    self_loops = True
+
     def __init__(self, ptr, idx, rel, pos, inv, n_dst, n_src, E, device, row=None):
         self.csr_ptr, self.csr_idx, self.rel, self.pos, self.inv = ptr, idx, rel, pos, inv
         self.row = row
@@ -62,15 +67,20 @@ class DeviceSampler:
     """Capacity-sized device sampler over a RelGraph (CSR by destination).
 
     etype: 0-based edge type per caller edge (mag edge_type), or None (relation 0);
-    ntype: node type per global node (self-loop relation num_edge_types + ntype), or None."""
+    ntype: node type per global node (self-loop relation num_edge_types + ntype), or None.
+    self_loops=False (mag self_loop_type 1 / 3): the hops append no self loop
+    (regnn_ns_hop_noloop) -- a row holds its sampled entries only, inv = 1 / max(sampled, 1), the
+    blocks carry ``self_loops = False``. CSR layout only: the strided layout, the transposed
+    index, the edge meta and the input sums are refused (ValueError)."""
 
     def __init__(self, rg, sizes, batch_size, etype=None, ntype=None, num_edge_types=0,
-                 share=None):
+                 share=None, self_loops=True):
         """share: another DeviceSampler over the same graph whose read-only tables (edge and
         node types) and dedup tables are reused (a second pipeline slot: the two never sample
         at the same time, and their dedup stamps never coincide)."""
         dev = rg.device
         self.rg, self.device = rg, dev
+        self.self_loops = bool(self_loops)
         self.sizes_k = [int(k) for k in sizes]
         if not self.sizes_k or any(k < 1 or k > 64 for k in self.sizes_k):
             raise ValueError(f"device sampler fan-outs must lie in [1, 64], got {sizes}")
@@ -130,6 +140,7 @@ class DeviceSampler:
                           torch.ones(cd, dtype=torch.float32, device=dev), cd, caps[h + 1], ce, dev,
                           row=z(ce))
             blk.state = self.state             # the batch's dropout key (the wide epilogue's)
+            blk.self_loops = self.self_loops
             self.blocks.append(blk)
         self.local, self.edge_meta = None, [None] * len(self.sizes_k)
         self.meta_fresh = [False] * len(self.sizes_k)
@@ -166,6 +177,7 @@ class DeviceSampler:
     def enable_edge_meta(self, local_node_idx, hop):
         """also write hop `hop`'s per-edge source node type and table row (regnn_ns_hop's
         optional outputs; what regnn_nsm_step's layer 0 gathers by)."""
+        self._need_loops("enable_edge_meta (the edge meta feeds the fused step's layer 0)")
         self.local = torch.as_tensor(local_node_idx).to(self.device, torch.int64).contiguous()
         ce = self.blocks[hop].csr_idx.numel()
         self.edge_meta[hop] = (torch.zeros(ce, dtype=torch.int32, device=self.device),
@@ -176,6 +188,7 @@ class DeviceSampler:
     def enable_csc(self, hop):
         """also build hop `hop`'s transposed index (regnn_ns_hop csc_*: per local source, its
         edges' target row << 8 | relation), what the fused step's transposed pass gathers by."""
+        self._need_loops("enable_csc (the sampler-built transposed index)")
         ce = self.blocks[hop].csr_idx.numel()
         if ce > 32768:
             raise ValueError(f"the transposed index needs <= 32768 block edges, got {ce}")
@@ -183,6 +196,23 @@ class DeviceSampler:
         self.csc[hop] = (z(ce), z(ce + 1), z(ce), z(max(ce + 1, CSC_LONG_INTS)))
         self.csc_rank[hop] = z(ce)
         return self.csc[hop]
+
+    def _need_loops(self, what):
+        if not self.self_loops:
+            raise ValueError(f"{what} is not built for a sampler with self_loops=False: "
+                             "regnn_ns_hop_noloop writes the CSR layout only, without edge meta, "
+                             "transposed index or input sums")
+
+    def _check_noloop(self, strided):
+        """a loop-less sampler's run_hops: every hop in the CSR layout, nothing beside the block"""
+        if strided or any(bool(s) for s in self.hop_strided):
+            self._need_loops("the fixed-stride layout (run_hops(strided=True) / hop_strided)")
+        if any(self.meta_only) or any(m is not None for m in self.edge_meta):
+            self._need_loops("enable_edge_meta / meta_only")
+        if any(t is not None for t in self.typed_sums):
+            self._need_loops("typed_sums (the sampler's layer-0 input sums)")
+        if any(c is not None for c in self.csc):
+            self._need_loops("enable_csc (the sampler-built transposed index)")
 
     def _csc_args(self, h):
         """regnn_ns_hop's csc_cnt .. csc_rank of hop h"""
@@ -203,6 +233,8 @@ class DeviceSampler:
         called right before the outer hop's sums launch (regnn_ns_hop_typed_sums), e.g. to make
         it wait on an event."""
         strided = self.strided if strided is None else bool(strided)
+        if not self.self_loops:
+            self._check_noloop(strided)
         # a hop's own layout (hop_strided[h] not None) wins over the call's: the module path
         # samples its outer hop strided with the input sums while hop 0 stays CSR
         hs = lambda h: strided if self.hop_strided[h] is None else self.hop_strided[h]  # noqa: E731
@@ -293,6 +325,15 @@ class DeviceSampler:
     def _hop_call(self, h, k, meta_only, mode):
         """regnn_ns_hop of hop h with its buffers; mode: the call's `strided`"""
         rg, b, blk = self.rg, self.hop_bufs[h], self.blocks[h]
+        if not self.self_loops:
+            L.call("regnn_ns_hop_noloop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx),
+                   L.ptr(self.etype_csr), L.ptr(self.ntype), self.num_edge_types, k, h,
+                   L.ptr(self.state), L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h],
+                   L.ptr(self.g2l), L.ptr(self.first), L.ptr(b["samp"]), L.ptr(b["spos"]),
+                   L.ptr(b["scnt"]), L.ptr(b["gsrc"]), L.ptr(b["flag"]), L.ptr(b["tiles"]),
+                   L.ptr(b["status"]), L.ptr(blk.csr_ptr), L.ptr(blk.csr_idx), L.ptr(blk.rel),
+                   L.ptr(blk.pos), L.ptr(blk.row), L.ptr(blk.inv), L.stream())
+            return
         L.call("regnn_ns_hop", L.ptr(rg.csr_ptr), L.ptr(rg.csr_idx), L.ptr(self.etype_csr),
                L.ptr(self.ntype), self.num_edge_types, k, h, L.ptr(self.state),
                L.ptr(self.sizes), L.ptr(self.n_id), self.caps[h], L.ptr(self.g2l),
@@ -358,7 +399,9 @@ class DeviceSampler:
             dst_l = dst_all[keep]
             e_id = self.rg.csr_eid[pos[keep].to(torch.int64)]
             eb = NSBlock(ptr, idx, rel, pos, inv, n_dst, n_src, E, self.device)
-            out.append((torch.stack([src_l, dst_l]), e_id, (n_src, n_dst), eb, cnt - 1))
+            eb.self_loops = self.self_loops
+            out.append((torch.stack([src_l, dst_l]), e_id, (n_src, n_dst), eb,
+                        cnt - 1 if self.self_loops else cnt))
         return sz[len(self.sizes_k)], out
 
 
@@ -486,18 +529,31 @@ def gat_blocks_unsupported(model, x_dict):
     (ops.BF16_ROWS "on": or all-bf16 ones, read by group_input's gather-fused Linear),
     1..16 heads and a head width that is a multiple of 4 in [4, 512]; and, with
     mag.GATV2_BLOCKS on, 'regatv2' (REGATv2Conv over ops.ns_gatv2) under the same conditions
-    and heads x head width <= 2048."""
+    and heads x head width <= 2048. self_loop_type 1 / 3 with mag.NOLOOP_BLOCKS on (loop-less
+    blocks, DeviceSampler(self_loops=False)): the same two attention models under the same
+    conditions and 'regcn' (use_norm 'bn' too, over the live rows), all three on fp32 tables
+    only; with that knob off (the default) types 1 / 3 are refused as before."""
     from . import mag, ops
     kind = getattr(model, "model", None)
+    slt = getattr(model, "self_loop_type", None)
+    noloop = slt in (1, 3) and mag.noloop_blocks_on()
+    if noloop and any(torch.is_tensor(x) and x.dtype != torch.float32
+                             for x in x_dict.values()):
+        return (f"self_loop_type {slt}: loop-less blocks read fp32 input tables (bf16 tables are "
+                "read through the sampler's input sums or ops.BF16_ROWS, neither built for them)")
+    if kind == "regcn" and noloop:
+        return None                            # (use_norm 'bn': NSTrainer checks ops.wide_bn_act)
     if kind == "regatv2" and mag.GATV2_BLOCKS["mode"] != "on":
         return ("regatv2: GATv2 scores have no device-block operator (ops.ns_gat covers "
                 "REGATConv only); it stays on the exact-size path")
     if kind not in ("regat", "regatv2"):
         return f"model {kind!r} is neither 'regcn' nor 'regat'"
     op = "ops.ns_gat" if kind == "regat" else "ops.ns_gatv2"
-    if getattr(model, "self_loop_type", None) != 2:
-        return (f"self_loop_type {getattr(model, 'self_loop_type', None)}: the sampler's blocks "
-                "carry self_loop_type 2's self loops (relation num_edge_types + node type)")
+    if slt != 2 and not noloop:
+        return (f"self_loop_type {slt}: the sampler's blocks "
+                "carry self_loop_type 2's self loops (relation num_edge_types + node type); "
+                "REGNN_NOLOOP_BLOCKS=on (mag.NOLOOP_BLOCKS) samples loop-less blocks for "
+                "types 1 / 3")
     for c in model.convs:
         if c.use_norm == "bn":
             return ("use_norm 'bn': batch statistics over the capacity-sized rows would include "
@@ -1193,12 +1249,23 @@ class NSTrainer:
         over ops.ns_gatv2, the same step: CSR hops, lookahead 1, two slots, one-step graphs);
         raises ValueError where the blocks do not cover the model (gat_blocks_unsupported:
         'regatv2' with the knob off among them). 'regcn' / self_loop_type 2 is on the blocks
-        either way."""
+        either way. A model of self_loop_type 1 / 3 ('regcn', 'regat', 'regatv2' with its knob
+        on) where mag.NOLOOP_BLOCKS is on: loop-less blocks (DeviceSampler(self_loops=False)) in
+        the same step shape; the fused step and bf16 input tables are refused. With
+        mag.NOLOOP_BLOCKS off (the default) such a model is refused here; without device_blocks
+        it keeps the exact-size path."""
         self.model, self.opt = model, opt
         dev = rg.device
         self.device, self.rank, self.world = dev, int(rank), int(world)
+        # self_loop_type 1 / 3 on device blocks: every slot samples without the appended loops
+        # (opt-in: mag.NOLOOP_BLOCKS; off: such a model is refused below, as before)
+        from . import mag as _mag
+        self._noloop = (bool(device_blocks) and
+                        getattr(model, "self_loop_type", None) in (1, 3) and
+                        _mag.noloop_blocks_on())
         self.slots = [DeviceSampler(rg, sizes, batch_size, etype=edge_type, ntype=node_type,
-                                    num_edge_types=num_edge_types)]
+                                    num_edge_types=num_edge_types,
+                                    self_loops=not self._noloop)]
         self.cur, self._primed, self._trained = 0, False, 0
         self.train_idx = torch.as_tensor(train_idx).to(dev, torch.int64)
         self.perm = self.train_idx.clone()
@@ -1221,17 +1288,25 @@ class NSTrainer:
             if why_not is not None:
                 raise ValueError(f"device_blocks=True does not cover this model: {why_not}")
             if engine == "fused":
-                raise ValueError("device_blocks=True: 'regat' runs on the module path, not the "
-                                 "fused step")
+                raise ValueError(
+                    "device_blocks=True: "
+                    + (f"a self_loop_type {model.self_loop_type} model" if self._noloop
+                       else "'regat'")
+                    + " runs on the module path, not the fused step"
+                    + (" (regnn_nsm_step aggregates self_loop_type 2's blocks only)"
+                       if self._noloop else ""))
+            # (a loop-less 'regcn' takes the attention models' step shape: every hop CSR,
+            # lookahead 1, two slots, one-step graphs)
             self._blocks_ok = self._gat_blocks = True
             # ops.NS_GAT_SRC "gather": every slot owns its hops' transposed-index buffers and
             # builds them beside the hops (_sample); the backwards then use no float atomics
             from . import ops as _ops
-            self._gat_src_gather = _ops.ns_gat_src_mode() == "gather"
+            self._gat_src_gather = (_ops.ns_gat_src_mode() == "gather" and
+                                    getattr(model, "model", None) != "regcn")
         # use_norm 'bn' on the capacity-sized blocks: the batch statistics are taken over the
         # block's live rows by ops.wide_bn_act, never by torch's BatchNorm1d over the padded rows;
         # where that operator does not cover a conv the trainer refuses (no silent fall-back)
-        if self._blocks_ok and not self._gat_blocks:
+        if self._blocks_ok and getattr(model, "model", None) == "regcn":
             from . import ops as _ops
             for i, c in enumerate(getattr(model, "convs", [])):
                 if getattr(c, "use_norm", None) != "bn":
@@ -1332,7 +1407,8 @@ class NSTrainer:
         if self.pipelined:
             for j in range(1, 2 * self.ahead):
                 self.slots.append(DeviceSampler(
-                    rg, sizes, batch_size, num_edge_types=num_edge_types, share=self.slots[0]))
+                    rg, sizes, batch_size, num_edge_types=num_edge_types, share=self.slots[0],
+                    self_loops=not self._noloop))
             if self.fused is not None:
                 self.fused_slots = [self.fused] + [
                     FusedStep(model, s, x_dict, node_type, local_node_idx, self.y_flat, self.loss)
@@ -1430,7 +1506,8 @@ class NSTrainer:
         if _ops_bf16_rows_on():
             return self._bf16_rows_unsupported()
         if not self._blocks_ok:
-            return "the model does not run on device blocks (regcn, self_loop_type 2)"
+            return ("the model does not run on device blocks (regcn, self_loop_type 2; "
+                    "device_blocks=True: regat / regatv2, self_loop_type 1 / 3)")
         if any(bool(getattr(c, "residual", False)) for c in m.convs):
             return ("the module path's residual convs project the raw rows (group_input), which "
                     "reads fp32 tables")

@@ -57,12 +57,15 @@ class NeighborSampler:
 
     edge_type / node_type / num_edge_types (optional): the blocks' relation ids are then formed
     by the sampler itself (mag self_loop_type 2: edge type, num_edge_types + node type for the
-    target's self loop)."""
+    target's self loop). self_loops=False (mag self_loop_type 1 / 3): the device sampler appends
+    no self loop (DeviceSampler(self_loops=False)), so a typed ``Adj.block`` carries edge types
+    only and its ``self_loops`` is False."""
 
     def __init__(self, rg, node_idx, sizes, batch_size, shuffle=True, seed=0, rank=0,
                  world_size=1, drop_last=False, edge_type=None, node_type=None,
-                 num_edge_types=0):
+                 num_edge_types=0, self_loops=True):
         self.rg = rg
+        self.self_loops = bool(self_loops)
         if node_idx is None:                       # PyG: every node is a target
             node_idx = torch.arange(rg.n_dst, device=rg.device)
         self.node_idx = torch.as_tensor(node_idx).to(rg.device, torch.int64)
@@ -118,7 +121,7 @@ class NeighborSampler:
                 self.rg, self.sizes, self.batch_size,
                 etype=self.edge_type if self.typed else None,
                 ntype=self.node_type if self.typed else None,
-                num_edge_types=self.num_edge_types)
+                num_edge_types=self.num_edge_types, self_loops=self.self_loops)
         return self._dev
 
     def sample(self, batch, batch_idx=0):
