@@ -1534,6 +1534,7 @@ class _GatV2Score(torch.autograd.Function):
 
 def gatv2_scores(rg, fs, fd, att, slope=0.2):
     """GATv2 attention logits per edge (CSR order): layer/REGATv2Conv.py:139-141."""
+    _refuse("gatv2_scores", gatv2_scores_ok(fs.shape[1], fs.shape[2]), fs.shape[1], fs.shape[2])
     return _GatV2Score.apply(fs, fd, att, rg, slope)
 
 
@@ -1582,6 +1583,7 @@ class _EdgeSoftmax(torch.autograd.Function):
 
 def edge_softmax_logits(rg, s, ee_tab=None, pack=None, global_max=False):
     """edge softmax of per-edge logits s [E, H] (CSR order) plus the relation bias ee[rel]."""
+    _refuse("edge_softmax_logits", edge_softmax_ok(s.shape[1]), s.shape[1])
     return _EdgeSoftmax.apply(s, ee_tab, rg, pack, global_max)
 
 
@@ -1763,12 +1765,49 @@ def gat_fused_ok(H):
     return H >= 1 and H & (H - 1) == 0 and H <= 32
 
 
+def heads_ok(H, D, dtype=torch.float32):
+    """(H, D) the per-head SpMM kernels take (dispatch_heads, re_gat.hip): D a multiple of the
+    16-byte vector (4 fp32 / 8 bf16 elements), D / vector a power of two <= 64 lanes and at most
+    64 x 8 vectors a row. The fused GAT forward alone takes more (any D % vector == 0), but its
+    backward runs regnn_spmm_heads_bwd, so gat_fused keeps to these shapes as well."""
+    ev = 8 if dtype == torch.bfloat16 else 4
+    if H < 1 or D < ev or D % ev:
+        return False
+    vph = D // ev
+    return vph & (vph - 1) == 0 and vph <= 64 and H * vph <= 512
+
+
+def gatv2_scores_ok(H, D):
+    """(H, D) regnn_gatv2_score_* take (launch_gatv2, re_gatv2.hip; fp32 rows): D / 4 a power of
+    two <= 64 and at most 64 x 4 vectors a row (H * D <= 1024); any head count."""
+    if H < 1 or D < 4 or D % 4:
+        return False
+    vph = D // 4
+    return vph & (vph - 1) == 0 and vph <= 64 and H * vph <= 256
+
+
+def edge_softmax_ok(H):
+    """head counts regnn_edge_softmax_* take (sm_log2, re_gatv2.hip): a power of two <= 32"""
+    return 1 <= H <= 32 and H & (H - 1) == 0
+
+
+def _refuse(op, ok, H, D=None, dtype=None):
+    """ValueError before any launch: a shape one kernel of an operator's chain refuses must not
+    yield a forward result whose backward then fails"""
+    if not ok:
+        shape = f"H={H}" + ("" if D is None else f", D={D}") + \
+            ("" if dtype is None else f", {str(dtype).replace('torch.', '')}")
+        raise ValueError(f"regnn_hip.ops.{op}: unsupported shape ({shape})")
+
+
 def gat_fused(rg, el, er, ft, ee_tab=None, pack=None, slope=0.2, attn_l=None, attn_drop=0.0,
               drop_seed=None):
     """layer/REGATConv.py:80-92 as one fused forward pass (H a power of two <= 32; otherwise the
     unfused gat_attention + head_spmm). With attn_l (el then being attn_dots(ft, attn_l, ...)'s)
     the kernel re-forms el from the rows it gathers, bitwise the same, instead of reading it per
-    edge (fp32 rows, D / 4 a power of two).
+    edge (fp32 rows, D / 4 a power of two no larger than the tier's lanes per row). Shapes:
+    heads_ok(H, D, ft.dtype), those its backward's per-head SpMM takes; others raise ValueError
+    here, not a forward result whose backward fails.
 
     attn_drop > 0: the attention dropout of :88 inside the same pass, out = sum_e (m_e / keep) a_e
     ft_u with a the undropped edge softmax and m this build's hash mask over (CSR edge position,
@@ -1777,6 +1816,7 @@ def gat_fused(rg, el, er, ft, ee_tab=None, pack=None, slope=0.2, attn_l=None, at
     drop_request, as the SpMM dropout does. Generic head counts run torch's dropout between the
     two unfused operators."""
     H = ft.shape[1]
+    _refuse("gat_fused", heads_ok(H, ft.shape[2], ft.dtype), H, ft.shape[2], ft.dtype)
     if not gat_fused_ok(H):
         a = gat_attention(rg, el, er, ee_tab, pack, slope)
         if attn_drop > 0:
@@ -1790,6 +1830,8 @@ def gat_fused(rg, el, er, ft, ee_tab=None, pack=None, slope=0.2, attn_l=None, at
 
 def head_spmm(rg, a, ft):
     """out[v,h,:] = sum_{e: u->v} a[e,h] * ft[u,h,:]   (a in CSR edge order)."""
+    _refuse("head_spmm", heads_ok(ft.shape[1], ft.shape[2], ft.dtype), ft.shape[1], ft.shape[2],
+            ft.dtype)
     return _HeadSpmm.apply(a, ft, rg)
 
 

@@ -1,6 +1,7 @@
 """fp64 references of the GAT / GATv2 attention kernels (re_gat.hip, re_gatv2.hip) with a
 per-element error scale, the input recipes and the ladder graph of the attention parity tests
-(test_cpu_attention_ref.py, test_gpu_gat_fused.py). A plain helper: no test lives here.
+(test_cpu_attention_ref.py, test_gpu_gat_fused.py, test_gpu_attention_matrix.py) and the table of
+the matrix's shapes. A plain helper: no test lives here.
 
 The restatements are torch code with autograd over the CSR edge list (ptr, idx, rel_csr):
   gat_reference    layer/REGATConv.py:80-92     (global_max: the softmax of mag/utils.py:45-57)
@@ -181,6 +182,50 @@ def gatv2_case_ref(ptr, idx, rel_csr, fs, fd, att, tab, ft, gy, slope, global_ma
     return want, scale
 
 
+def gatv2_shared_case_ref(ptr, idx, rel_csr, x, att, tab, gy, slope, global_max=False):
+    """the GATv2 kinds with fs, fd and ft ONE leaf x (layer/REGATv2Conv.py share_weights=True on
+    a graph whose sources are its destinations): out, g_x, g_att[, g_tab]. g_x is the sum of the
+    three partial gradients, so its scale is the sum of their scales."""
+    x, att, tab = _leaves([x, att, tab])
+    gy = gy.detach().double()
+    out = gatv2_reference(ptr, idx, rel_csr, x, x, att, tab, x, slope, global_max)
+    out.backward(gy)
+    want = {"out": out.detach(), "g_x": x.grad, "g_att": att.grad}
+    _, part = gatv2_case_ref(ptr, idx, rel_csr, x, x, att, tab, x, gy, slope, global_max)
+    scale = {"out": part["out"], "g_x": part["g_fs"] + part["g_fd"] + part["g_ft"],
+             "g_att": part["g_att"]}
+    if tab is not None:
+        want["g_tab"], scale["g_tab"] = tab.grad, part["g_tab"]
+    return want, scale
+
+
+def gatv2_score_ref(ptr, idx, fs, fd, att, slope):
+    """s[e,h] = <att[h], LeakyReLU(fs[u,h] + fd[v,h])> in CSR edge order, in the inputs' dtype"""
+    src, dst, _ = _edges(ptr, idx)
+    return (F.leaky_relu(fs[src] + fd[dst], slope) * att).sum(-1)
+
+
+def gatv2_score_case_ref(ptr, idx, fs, fd, att, gs, slope):
+    """fp64 reference and scale of the score operator alone (loss = sum gs * s): s, g_fs, g_fd,
+    g_att. s[e,h] is measured against sum_d |att LeakyReLU(fs_u + fd_v)|, the gradients against
+    the sums of |gs| |att| LeakyReLU' and |gs| |LeakyReLU|."""
+    fs, fd, att = _leaves([fs, fd, att])
+    gs = gs.detach().double()
+    s = gatv2_score_ref(ptr, idx, fs, fd, att, slope)
+    s.backward(gs)
+    want = {"s": s.detach(), "g_fs": fs.grad, "g_fd": fd.grad, "g_att": att.grad}
+    src, dst, _ = _edges(ptr, idx)
+    with torch.no_grad():
+        pre = fs[src] + fd[dst]
+        act = F.leaky_relu(pre, slope).abs()
+        through = gs.abs()[:, :, None] * att.abs() * torch.where(pre > 0, 1.0, slope)
+        scale = {"s": (act * att.abs()).sum(-1),
+                 "g_fs": torch.zeros_like(fs).index_add(0, src, through),
+                 "g_fd": torch.zeros_like(fd).index_add(0, dst, through),
+                 "g_att": (gs.abs()[:, :, None] * act).sum(0, keepdim=True)}
+    return want, scale
+
+
 # ---- the metric --------------------------------------------------------------------------------
 def rel_err(got, ref, scale, bf16_store=False):
     """max |got - ref| / (scale + 2^-100); bf16_store: |got - ref| less the rounding of a bf16
@@ -264,6 +309,38 @@ def gatv2_inputs(recipe, N, H, D, n_rel, seed):
     elif recipe != "unit":
         raise ValueError(recipe)
     return fs, fd, att, tab, ft, gy, slope
+
+
+def gatv2_shared_inputs(N, H, D, n_rel, seed):
+    """(x, att, tab, gy, slope) of the shared-leaf GATv2 case: gatv2_inputs' `unit` tensors with
+    x = its fs (randn * 0.5: x + x keeps the scores O(1))."""
+    fs, _, att, tab, _, gy, slope = gatv2_inputs("unit", N, H, D, n_rel, seed)
+    return fs, att, tab, gy, slope
+
+
+def score_grad(E, H, seed):
+    """gs [E, H], the incoming gradient of the score operator's own case"""
+    return _randn(torch.Generator().manual_seed(seed + 77), E, H)
+
+
+# ---- the shapes of the parity matrix (test_cpu_attention_ref.py guards every one of them,
+# test_gpu_attention_matrix.py / test_gpu_gat_fused.py run them) ---------------------------------
+# every fp32 (H, D): one or two per dispatch tier, H = 16 / 32, generic head counts
+SHAPES = [(1, 4), (4, 16), (8, 16), (1, 128), (16, 16), (32, 8), (8, 64), (2, 256), (16, 64),
+          (32, 64), (3, 4), (6, 8), (12, 16), (64, 4)]
+WIDE = [(4, 16), (32, 8), (3, 4)]                     # shapes that also run the `wide` recipe
+POW2_SHAPES = [(H, D) for H, D in SHAPES if H & (H - 1) == 0 and H <= 32]
+V2_SHAPES = [(H, D) for H, D in POW2_SHAPES if H * D <= 1024]
+# bf16 rows (8 elements per vector): the tiers (16,1) (16,1) (16,2) (16,4) (64,2) (64,4) (64,8)
+BF16_SHAPES = [(1, 8), (8, 16), (16, 16), (8, 64), (16, 64), (32, 64), (32, 128)]
+SHARED_SHAPES = [(4, 16), (8, 64)]                    # GATv2 with fs, fd, ft one leaf
+# the direct per-edge checks, scale |reference|: the attention a of both recipes, the GATv2 score
+# s of `wide` alone (exact in fp32). s of `unit` is a dot with cancellation: under |reference| its
+# fp32 restatement is off by 3.7e-5 .. 1.5e-3 on these shapes, far past TOL_GUARD, so it is left
+# out of that scale and runs under the scale of its terms instead (gatv2_score_case_ref).
+DIRECT_SHAPES = [(1, 4), (8, 64), (32, 8)]
+# the boundary shape the score operator takes on its own (H = 3: the edge softmax refuses it)
+SCORE_SHAPES = DIRECT_SHAPES + [(3, 8)]
 
 
 # ---- the ladder graph --------------------------------------------------------------------------
